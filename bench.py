@@ -10,8 +10,14 @@ correlation work (corr.py:116-208 called as raft_dvc.py:414-450 calls it):
     12 lookups with 12 different coordinate fields               12 x CorrBlock.__call__
 value = 12 * (query voxels of the whole job) * steps / wall time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (what the driver runs)
+
+A plain run sets up, runs W warm-up and K timed steps and prints the headline line (value, ms_per_step and the
+configuration); --dump-outputs DIR also writes the last timed step's lookup outputs as DIR/lookup_<i>.npy (the
+inputs are seeded, so two builds can be compared output for output).  --full adds every measurement that takes
+runs of its own after the timed steps: per-kernel times and roofline, flow_step, backward, cpu_baseline and, at
+N>1, scaling_detail.
 
 `--gpus N` without a torchrun environment spawns torch.distributed.run with N
 ranks as a child process (this parent never touches the GPU) and exits with
@@ -22,14 +28,15 @@ voxels are split into N H-slabs, one per rank; each rank all-gathers the fmap2
 slabs (RCCL, the data-path collective), builds only its own rows of every
 level and looks up its own queries; lookups stay shard-resident.  The per-rank
 step after the collective is replayed as a HIP graph (--no-graph: eager).
-At N>1 the line also carries `scaling_detail`, measured in the same job:
+At N>1 the --full line also carries `scaling_detail`, measured in the same job:
 T1 (rank 0 alone on the whole problem), the strong layout with every lookup
 all-gathered (--gather-output), weak scaling (one pair per rank) and config #4
 (256^3 input, 1/4 encoder: 64^3 fmaps) strong-scaled, each with E(n) =
 T1 / (n * Tn).
 
-Prints one JSON line (rank 0) with roofline (dominant kernel, HIP-event timed
-on its stream) and cpu_baseline (oracle/torch_cpu.py on the host, N=1).
+Prints one JSON line (rank 0); with --full it holds roofline (dominant kernel,
+HIP-event timed on its stream) and cpu_baseline (oracle/torch_cpu.py on the
+host, N=1) as well.
 """
 from __future__ import annotations
 
@@ -49,6 +56,7 @@ sys.path.insert(0, os.path.join(ROOT, "raft-dvc_amd"))
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md)
 BF16_PEAK_TFS = 2500.0         # dense bf16 MFMA
 F32_PEAK_TFS = 157.3           # f32 MFMA / vector
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs writes at most this much in all
 
 
 def parse(argv=None):
@@ -56,6 +64,12 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: per-kernel times and roofline, "
+                         "flow_step, backward, cpu_baseline and (N>1) scaling_detail")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's lookup outputs as DIR/<name>.npy (fp32; a "
+                         "fixed, seeded sample of the query columns where the whole would exceed DUMP_BUDGET_BYTES)")
     ap.add_argument("--size", type=int, default=32, help="feature-map edge (32 = 128^3 input, 1/4 encoder)")
     ap.add_argument("--encoder", type=int, default=4, help="encoder downsampling (input edge = size x encoder)")
     ap.add_argument("--channels", type=int, default=128)
@@ -91,13 +105,13 @@ def parse(argv=None):
     ap.add_argument("--graph", dest="graph", action="store_true", default=True,
                     help="replay each rank's post-collective step as a HIP graph (default)")
     ap.add_argument("--no-graph", dest="graph", action="store_false")
-    ap.add_argument("--no-extras", action="store_true", help="N>1: skip scaling_detail (T1, gather, weak, cfg #4)")
+    ap.add_argument("--no-extras", action="store_true", help="--full at N>1: skip scaling_detail (T1, gather, weak, cfg #4)")
     ap.add_argument("--cfg4-steps", type=int, default=3, help="N>1: timed steps of the config #4 extra (0: off)")
     ap.add_argument("--shard-of", type=int, default=1,
                     help="diagnostics on one GPU: time rank --shard-rank's slab of an N-way split alone "
                          "(its per-rank compute; fmap2 is given whole, no collective)")
     ap.add_argument("--shard-rank", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
     ap.add_argument("--tune", default="", help="diagnostics: comma list key=value of dvc_set_tuning knobs")
     ap.add_argument("--cpu-rows", type=int, default=4096, help="query rows of the bounded CPU sample")
     ap.add_argument("--coord-fields", type=int, default=0,
@@ -220,7 +234,8 @@ class Runner:
             self.bufs = [all_gather_slab(self.f2_slab, H, group) for _ in range(2 if self.overlap else 1)]
         self.use_graph = graph and not self.gather_output
         self.graphs = [None, None]
-        self.outs = None
+        self.graph_outs = [None, None]   # each graph's static output tensors
+        self.outs = None      # the last step's outputs (what a caller of the step receives)
         self.k = 0            # step counter (selects the receive buffer)
         self.pending = None   # async work handle of the next step's gather
 
@@ -279,7 +294,7 @@ class Runner:
         torch.cuda.empty_cache()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self.outs = self.compute(slot=slot)
+            self.graph_outs[slot] = self.compute(slot=slot)
         self.graphs[slot] = g
 
     def _run(self, slot):
@@ -287,6 +302,7 @@ class Runner:
             if self.graphs[slot] is None:
                 self.capture(slot)
             self.graphs[slot].replay()
+            self.outs = self.graph_outs[slot]
         else:
             self.outs = self.compute(slot=slot)
 
@@ -313,6 +329,7 @@ class Runner:
     def release(self):
         self.drain()
         self.graphs = [None, None]
+        self.graph_outs = [None, None]
         self.outs = None
         self.bufs = [None, None]
 
@@ -342,6 +359,23 @@ def timed(runner, steps, warmup, dist, dev, participate=True):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     return elapsed
+
+
+def dump_outputs(path, outs, rank=0, world=1, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: the step's lookup outputs, each (B, channels, queries), as fp32 lookup_00.npy, ... in call
+    order (at N>1 every rank writes its own shard's: lookup_00_rank<r>.npy).  An output larger than its share of
+    `budget` is written as a sample of its query columns: one seeded choice, sorted, the same in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = budget // (4 * world * len(outs))            # fp32 elements per file
+    for i, o in enumerate(outs):
+        o = o.detach().reshape(o.shape[0], o.shape[1], -1)
+        keep = max(1, share // (o.shape[0] * o.shape[1]))
+        if keep < o.shape[2]:
+            idx = torch.randperm(o.shape[2], generator=torch.Generator().manual_seed(4321))[:keep].sort().values
+            o = o.index_select(2, idx.to(o.device))
+        name = f"lookup_{i:02d}" + (f"_rank{rank}" if world > 1 else "") + ".npy"
+        np.save(os.path.join(path, name), o.float().cpu().numpy())
 
 
 def synthetic_flow(kind, B, S, max_flow, g):
@@ -440,135 +474,138 @@ def main():
     runner = Runner(f1_slab, f2_slab, coords_slab, S, args, group, world, gather_output=args.gather_output,
                     graph=args.graph, proj=proj, overlap=args.overlap)
     elapsed = timed(runner, args.steps, args.warmup, dist, dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, runner.outs, rank, world)
     runner.release()
     ms_per_step = elapsed * 1e3 / args.steps
     value = args.iters * nq_total * args.steps / elapsed
 
-    # per-kernel HIP-event timing on the launch stream: eager steps after the timed region
-    ev = {"lookup": [], "build": []}
-    with torch.no_grad():
-        er = Runner(f1_slab, f2_slab, coords_slab, S, args, group, world, graph=False, proj=proj)
-        for k in range(4):
-            er.collective()
-            er.compute(ev if k > 0 else None, stream)
-        torch.cuda.synchronize()
-        er.release()
-        del er
-    lk_ms = [a.elapsed_time(b) for a, b in ev["lookup"]]
-    bd_ms = [a.elapsed_time(b) for a, b in ev["build"]]
-    lk_avg = sum(lk_ms) / max(len(lk_ms), 1)
-    bd_avg = sum(bd_ms) / max(len(bd_ms), 1)
+    if args.full:   # everything beside the headline takes GPU or host runs of its own
+        # per-kernel HIP-event timing on the launch stream: eager steps after the timed region
+        ev = {"lookup": [], "build": []}
+        with torch.no_grad():
+            er = Runner(f1_slab, f2_slab, coords_slab, S, args, group, world, graph=False, proj=proj)
+            for k in range(4):
+                er.collective()
+                er.compute(ev if k > 0 else None, stream)
+            torch.cuda.synchronize()
+            er.release()
+            del er
+        lk_ms = [a.elapsed_time(b) for a, b in ev["lookup"]]
+        bd_ms = [a.elapsed_time(b) for a, b in ev["build"]]
+        lk_avg = sum(lk_ms) / max(len(lk_ms), 1)
+        bd_avg = sum(bd_ms) / max(len(bd_ms), 1)
 
-    # roofline of the dominant kernel (by time per step, rank 0's view)
-    lk_bytes = sum(lookup_algorithmic_bytes(c, dims, R, store_bytes if args.impl == "materialised" else 0,
-                                            96 * 4.0 if args.convc1 == "fused" else None)
-                   for c in coords_slab) / len(coords_slab)
-    unpadded = sum(h * w * d for (h, w, d) in dims)
-    n_targets = S * S * S
-    if args.impl == "materialised":
-        bd_bytes = nq_local * unpadded * store_bytes + 2 * C * 4 * n_targets
-        bd_flops = 2.0 * nq_local * n_targets * C
-    else:   # fused: the "build" only packs fmap1 rows and the pooled fmap2 pyramid (read f32, write bf16/f32)
-        bd_bytes = (nq_local + n_targets) * C * 4 + (nq_local + unpadded) * C * store_bytes
-        bd_flops = 0.0
-    traffic = traffic_src = None
-    if os.path.exists(args.traffic_file) and not shard_diag and args.flow == "random":   # PMC passes are per workload
-        try:
-            tf = json.load(open(args.traffic_file))
-            key = f"{args.impl}_{args.precision}_{S}_L{L}_r{R}_n{world if strong else 1}" + \
-                (f"_convc1_{args.convc1}" if args.convc1 else "")
-            traffic = tf.get(key, {}).get("lookup_hbm_bytes_per_launch")
-            traffic_src = tf.get(key, {}).get("note") if traffic is not None else None
-        except Exception:
-            traffic = None
-    lk_roof = lk_bytes / (lk_avg * 1e-3) / 1e9 if lk_avg else 0.0
-    if args.iters * lk_avg >= bd_avg or args.impl == "fused":
-        achieved = lk_roof
+        # roofline of the dominant kernel (by time per step, rank 0's view)
+        lk_bytes = sum(lookup_algorithmic_bytes(c, dims, R, store_bytes if args.impl == "materialised" else 0,
+                                                96 * 4.0 if args.convc1 == "fused" else None)
+                       for c in coords_slab) / len(coords_slab)
+        unpadded = sum(h * w * d for (h, w, d) in dims)
+        n_targets = S * S * S
         if args.impl == "materialised":
-            kname = {"fused": "k_lookup_tile<PROJ> (dvc_corr_lookup_proj, convc1 fused)",
-                     "unfused": "k_lookup_tile (dvc_corr_lookup) + torch conv/relu (timed together)"}.get(
-                         args.convc1, "k_lookup_tile (dvc_corr_lookup)")
-        elif args.convc1 == "fused" and sixteen and 1 <= R <= 4:
-            kname = ("k_otf_keys + radix sort + k_fused_proj + k_rows_to_channels "
-                     "(dvc_corr_lookup_fused_proj, convc1 fused, timed together)")
-        elif sixteen and 1 <= R <= 4:
-            kname = "k_fused_box (dvc_corr_lookup_fused)"
-        elif 1 <= R <= 4 and "fused_variant=0" not in args.tune:
-            kname = "k_fused_box_f32 (dvc_corr_lookup_fused; fp32 operands as three bf16 pieces, six MFMAs per step)"
+            bd_bytes = nq_local * unpadded * store_bytes + 2 * C * 4 * n_targets
+            bd_flops = 2.0 * nq_local * n_targets * C
+        else:   # fused: the "build" only packs fmap1 rows and the pooled fmap2 pyramid (read f32, write bf16/f32)
+            bd_bytes = (nq_local + n_targets) * C * 4 + (nq_local + unpadded) * C * store_bytes
+            bd_flops = 0.0
+        traffic = traffic_src = None
+        if os.path.exists(args.traffic_file) and not shard_diag and args.flow == "random":   # PMC passes are per workload
+            try:
+                tf = json.load(open(args.traffic_file))
+                key = f"{args.impl}_{args.precision}_{S}_L{L}_r{R}_n{world if strong else 1}" + \
+                    (f"_convc1_{args.convc1}" if args.convc1 else "")
+                traffic = tf.get(key, {}).get("lookup_hbm_bytes_per_launch")
+                traffic_src = tf.get(key, {}).get("note") if traffic is not None else None
+            except Exception:
+                traffic = None
+        lk_roof = lk_bytes / (lk_avg * 1e-3) / 1e9 if lk_avg else 0.0
+        if args.iters * lk_avg >= bd_avg or args.impl == "fused":
+            achieved = lk_roof
+            if args.impl == "materialised":
+                kname = {"fused": "k_lookup_tile<PROJ> (dvc_corr_lookup_proj, convc1 fused)",
+                         "unfused": "k_lookup_tile (dvc_corr_lookup) + torch conv/relu (timed together)"}.get(
+                             args.convc1, "k_lookup_tile (dvc_corr_lookup)")
+            elif args.convc1 == "fused" and sixteen and 1 <= R <= 4:
+                kname = ("k_otf_keys + radix sort + k_fused_proj + k_rows_to_channels "
+                         "(dvc_corr_lookup_fused_proj, convc1 fused, timed together)")
+            elif sixteen and 1 <= R <= 4:
+                kname = "k_fused_box (dvc_corr_lookup_fused)"
+            elif 1 <= R <= 4 and "fused_variant=0" not in args.tune:
+                kname = "k_fused_box_f32 (dvc_corr_lookup_fused; fp32 operands as three bf16 pieces, six MFMAs per step)"
+            else:
+                kname = "k_fused_dots + k_lookup_win (dvc_corr_lookup_fused)"
+            roof = {"kernel": kname,
+                    "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                    "algorithmic_bytes_per_launch": lk_bytes, "avg_launch_ms": round(lk_avg, 4),
+                    "traffic_source": traffic_src}   # which PMC pass (file, tree) the traffic figure comes from
+            if args.impl == "fused":
+                # the reference OTF dot count 2 C (2r+1)^3 L per voxel-query, against the dtype's MFMA peak
+                fl = 2.0 * C * (2 * R + 1) ** 3 * L * nq_local
+                peak = BF16_PEAK_TFS if sixteen else F32_PEAK_TFS   # (fp16 MFMA: the bf16 rate)
+                if args.convc1 == "fused":   # + convc1: 2 x 96 x L (2r+1)^3 per voxel-query
+                    fl += 2.0 * 96 * (2 * R + 1) ** 3 * L * nq_local
+                roof["mfma"] = {"achieved": round(fl / (lk_avg * 1e-3) / 1e12, 1), "peak": peak, "unit": "TFLOP/s",
+                                "frac": round(fl / (lk_avg * 1e-3) / 1e12 / peak, 4), "flops_per_launch": fl}
+                if args.convc1 == "fused":
+                    # nothing per lookup channel reaches HBM (96 fp32 per query out): the bound is the matrix
+                    # cores, so the top-level roofline is the MFMA one and the HBM numbers move to a sub-block
+                    hbm = {k: roof[k] for k in ("achieved", "peak", "unit", "frac", "traffic")}
+                    roof.update({"bound": "mfma", "achieved": roof["mfma"]["achieved"], "peak": peak,
+                                 "unit": "TFLOP/s", "frac": roof["mfma"]["frac"], "traffic": None, "hbm": hbm})
         else:
-            kname = "k_fused_dots + k_lookup_win (dvc_corr_lookup_fused)"
-        roof = {"kernel": kname,
-                "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                "algorithmic_bytes_per_launch": lk_bytes, "avg_launch_ms": round(lk_avg, 4),
-                "traffic_source": traffic_src}   # which PMC pass (file, tree) the traffic figure comes from
-        if args.impl == "fused":
-            # the reference OTF dot count 2 C (2r+1)^3 L per voxel-query, against the dtype's MFMA peak
-            fl = 2.0 * C * (2 * R + 1) ** 3 * L * nq_local
-            peak = BF16_PEAK_TFS if sixteen else F32_PEAK_TFS   # (fp16 MFMA: the bf16 rate)
-            if args.convc1 == "fused":   # + convc1: 2 x 96 x L (2r+1)^3 per voxel-query
-                fl += 2.0 * 96 * (2 * R + 1) ** 3 * L * nq_local
-            roof["mfma"] = {"achieved": round(fl / (lk_avg * 1e-3) / 1e12, 1), "peak": peak, "unit": "TFLOP/s",
-                            "frac": round(fl / (lk_avg * 1e-3) / 1e12 / peak, 4), "flops_per_launch": fl}
-            if args.convc1 == "fused":
-                # nothing per lookup channel reaches HBM (96 fp32 per query out): the bound is the matrix
-                # cores, so the top-level roofline is the MFMA one and the HBM numbers move to a sub-block
-                hbm = {k: roof[k] for k in ("achieved", "peak", "unit", "frac", "traffic")}
-                roof.update({"bound": "mfma", "achieved": roof["mfma"]["achieved"], "peak": peak,
-                             "unit": "TFLOP/s", "frac": roof["mfma"]["frac"], "traffic": None, "hbm": hbm})
-    else:
-        # the bf16 build (C = 128) is HBM-write-bound (~112 FLOP/B < ridge ~312); the exact-f32
-        # build is bound by the f32 matrix cores (~56 FLOP/B > ridge ~20): report each against its own roof
-        gbs = bd_bytes / (bd_avg * 1e-3) / 1e9
-        tfs = bd_flops / (bd_avg * 1e-3) / 1e12
-        lk = {"achieved": round(lk_roof, 1), "frac": round(lk_roof / HBM_PEAK_GBS, 4),
-              "algorithmic_bytes_per_launch": lk_bytes, "avg_launch_ms": round(lk_avg, 4)}
-        if args.precision == "fp32":
-            roof = {"kernel": "build (pack + k_build_f32r, exact-f32 MFMA v_mfma_f32_32x32x2_f32, register-resident "
-                              "targets)", "bound": "mfma",
-                    "achieved": round(tfs, 1), "peak": F32_PEAK_TFS, "unit": "TFLOP/s",
-                    "frac": round(tfs / F32_PEAK_TFS, 4), "traffic": None, "flops_per_launch": bd_flops,
-                    "avg_launch_ms": round(bd_avg, 4),
-                    "hbm": {"achieved": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 4),
-                            "algorithmic_bytes_per_launch": bd_bytes},
-                    "lookup": lk}
-        else:
-            roof = {"kernel": f"build (pack + k_build_bf16_2b, {args.precision})", "bound": "hbm", "achieved": round(gbs, 1),
-                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": None,
-                    "algorithmic_bytes_per_launch": bd_bytes, "avg_launch_ms": round(bd_avg, 4),
-                    "mfma": {"achieved": round(tfs, 1), "peak": BF16_PEAK_TFS,
-                             "frac": round(tfs / BF16_PEAK_TFS, 4), "flops_per_launch": bd_flops},
-                    "lookup": lk}
-    build_info = {"avg_ms": round(bd_avg, 4), "GB/s": round(bd_bytes / (bd_avg * 1e-3) / 1e9, 1) if bd_avg else None,
-                  "TFLOP/s": round(bd_flops / (bd_avg * 1e-3) / 1e12, 1) if bd_avg and bd_flops else None}
-    if bd_avg and bd_flops:   # each build against its binding roof
-        build_info["roof"] = ("f32 mfma" if args.precision == "fp32" else "hbm write")
-        build_info["frac"] = round(bd_flops / (bd_avg * 1e-3) / 1e12 / F32_PEAK_TFS, 4) if args.precision == "fp32" \
-            else round(bd_bytes / (bd_avg * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+            # the bf16 build (C = 128) is HBM-write-bound (~112 FLOP/B < ridge ~312); the exact-f32
+            # build is bound by the f32 matrix cores (~56 FLOP/B > ridge ~20): report each against its own roof
+            gbs = bd_bytes / (bd_avg * 1e-3) / 1e9
+            tfs = bd_flops / (bd_avg * 1e-3) / 1e12
+            lk = {"achieved": round(lk_roof, 1), "frac": round(lk_roof / HBM_PEAK_GBS, 4),
+                  "algorithmic_bytes_per_launch": lk_bytes, "avg_launch_ms": round(lk_avg, 4)}
+            if args.precision == "fp32":
+                roof = {"kernel": "build (pack + k_build_f32r, exact-f32 MFMA v_mfma_f32_32x32x2_f32, register-resident "
+                                  "targets)", "bound": "mfma",
+                        "achieved": round(tfs, 1), "peak": F32_PEAK_TFS, "unit": "TFLOP/s",
+                        "frac": round(tfs / F32_PEAK_TFS, 4), "traffic": None, "flops_per_launch": bd_flops,
+                        "avg_launch_ms": round(bd_avg, 4),
+                        "hbm": {"achieved": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 4),
+                                "algorithmic_bytes_per_launch": bd_bytes},
+                        "lookup": lk}
+            else:
+                roof = {"kernel": f"build (pack + k_build_bf16_2b, {args.precision})", "bound": "hbm", "achieved": round(gbs, 1),
+                        "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": None,
+                        "algorithmic_bytes_per_launch": bd_bytes, "avg_launch_ms": round(bd_avg, 4),
+                        "mfma": {"achieved": round(tfs, 1), "peak": BF16_PEAK_TFS,
+                                 "frac": round(tfs / BF16_PEAK_TFS, 4), "flops_per_launch": bd_flops},
+                        "lookup": lk}
+        build_info = {"avg_ms": round(bd_avg, 4), "GB/s": round(bd_bytes / (bd_avg * 1e-3) / 1e9, 1) if bd_avg else None,
+                      "TFLOP/s": round(bd_flops / (bd_avg * 1e-3) / 1e12, 1) if bd_avg and bd_flops else None}
+        if bd_avg and bd_flops:   # each build against its binding roof
+            build_info["roof"] = ("f32 mfma" if args.precision == "fp32" else "hbm write")
+            build_info["frac"] = round(bd_flops / (bd_avg * 1e-3) / 1e12 / F32_PEAK_TFS, 4) if args.precision == "fp32" \
+                else round(bd_bytes / (bd_avg * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
 
-    if rank == 0 and world == 1 and not shard_diag and roof.get("bound") == "hbm" and roof.get("unit") == "GB/s":
-        # context for the HBM fraction: the plain device copy rate of this box (read + write bytes), and the
-        # kernel's counter traffic per launch at its measured time, against it (traffic from the PMC file above)
-        cp = copy_rate(dev, stream)
-        roof["same_box_copy"] = cp
-        if roof.get("traffic"):
-            tr = roof["traffic"] / (roof["avg_launch_ms"] * 1e-3) / 1e9
-            roof["traffic_gbs"] = round(tr, 1)
-            roof["traffic_frac_of_copy"] = round(tr / cp["GB/s"], 3)
-    tail = flow_tail(args, coords_slab, S, B, dev, stream, _lib, dvccorr)
-    bwd = bwd_amp = None
-    if world == 1 and not shard_diag and args.convc1 is None:
-        bwd = backward_timing(args, f1_slab, f2_slab, coords_slab, dims, dev, stream)
-        # the reference Trainer's AMP backward (fp16 pyramid, trainer.py:249-257) on the same inputs
-        bwd_amp = backward_timing(args, f1_slab, f2_slab, coords_slab, dims, dev, stream, "fp16")
+        if rank == 0 and world == 1 and not shard_diag and roof.get("bound") == "hbm" and roof.get("unit") == "GB/s":
+            # context for the HBM fraction: the plain device copy rate of this box (read + write bytes), and the
+            # kernel's counter traffic per launch at its measured time, against it (traffic from the PMC file above)
+            cp = copy_rate(dev, stream)
+            roof["same_box_copy"] = cp
+            if roof.get("traffic"):
+                tr = roof["traffic"] / (roof["avg_launch_ms"] * 1e-3) / 1e9
+                roof["traffic_gbs"] = round(tr, 1)
+                roof["traffic_frac_of_copy"] = round(tr / cp["GB/s"], 3)
+        tail = flow_tail(args, coords_slab, S, B, dev, stream, _lib, dvccorr)
+        bwd = bwd_amp = None
+        if world == 1 and not shard_diag and args.convc1 is None:
+            bwd = backward_timing(args, f1_slab, f2_slab, coords_slab, dims, dev, stream)
+            # the reference Trainer's AMP backward (fp16 pyramid, trainer.py:249-257) on the same inputs
+            bwd_amp = backward_timing(args, f1_slab, f2_slab, coords_slab, dims, dev, stream, "fp16")
 
-    detail = None
-    if dist and strong and not args.no_extras:
-        detail = scaling_detail(args, f1, f2, coords_list, ms_per_step, world, rank, dev, dist, group, proj)
+        detail = None
+        if dist and strong and not args.no_extras:
+            detail = scaling_detail(args, f1, f2, coords_list, ms_per_step, world, rank, dev, dist, group, proj)
 
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not shard_diag:
-        cpu = cpu_baseline(args, f1, f2, coords_list)
+        cpu = None
+        if rank == 0 and world == 1 and not args.no_cpu_baseline and not shard_diag:
+            cpu = cpu_baseline(args, f1, f2, coords_list)
 
     if rank == 0:
         coll = "RCCL" if args.dist_backend == "nccl" else f"{args.dist_backend} (REHEARSAL, not RCCL)"
@@ -594,16 +631,19 @@ def main():
                        "collective": ("next step's fmap2 all-gather overlapped with this step's compute"
                                       if runner.overlap else "fmap2 all-gather before the step's compute"
                                       if runner.world > 1 else None)},
-            "roofline": roof,
-            "build": build_info,
-            "lookup_avg_ms": round(lk_avg, 4),
-            "flow_step": tail,
-            "backward": bwd,
-            "backward_amp": bwd_amp,
-            "cpu_baseline": cpu,
         }
-        if detail is not None:
-            line["scaling_detail"] = detail
+        if args.full:
+            line.update({
+                "roofline": roof,
+                "build": build_info,
+                "lookup_avg_ms": round(lk_avg, 4),
+                "flow_step": tail,
+                "backward": bwd,
+                "backward_amp": bwd_amp,
+                "cpu_baseline": cpu,
+            })
+            if detail is not None:
+                line["scaling_detail"] = detail
         print(json.dumps(line), flush=True)
     if dist:
         torch.distributed.destroy_process_group()

@@ -5,6 +5,7 @@ from __future__ import annotations
 import os
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -39,6 +40,39 @@ def test_world_size_must_match(monkeypatch):
 def test_defaults_are_strong_scaling_graph_replay():
     a = bench.parse([])
     assert a.scaling == "strong" and a.graph and a.gpus == 1 and a.size == 32 and a.levels == 4
+
+
+def test_plain_run_is_the_default():
+    """--full (the measurements beside the headline) and --dump-outputs are off unless asked for."""
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "d", "--steps", "7"])
+    assert a.full is True and a.dump_outputs == "d" and a.steps == 7
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """Small outputs are written whole, large ones as the same sorted sample of query columns in every run; all
+    fp32 and within the budget."""
+    g = torch.Generator().manual_seed(3)
+    outs = [torch.randn(1, 6, 50, generator=g), torch.randn(1, 6, 2, 5, 5, generator=g)]
+    bench.dump_outputs(str(tmp_path / "whole"), outs)
+    for i, o in enumerate(outs):
+        got = np.load(tmp_path / "whole" / f"lookup_{i:02d}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, o.reshape(1, 6, 50).numpy())
+    budget = 2 * 6 * 20 * 4                                # 20 of the 50 columns of each output
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs, budget=budget)
+    total = 0
+    for i, o in enumerate(outs):
+        a, b = (np.load(tmp_path / d / f"lookup_{i:02d}.npy") for d in ("a", "b"))
+        assert a.shape == (1, 6, 20) and a.dtype == np.float32 and np.array_equal(a, b)
+        full = o.reshape(1, 6, 50).numpy()
+        cols = [int(np.flatnonzero((full[0] == a[0][:, j:j + 1]).all(0))[0]) for j in range(20)]
+        assert cols == sorted(set(cols))                   # distinct columns of the output, in order
+        total += a.nbytes
+    assert total <= budget
+    bench.dump_outputs(str(tmp_path / "r"), outs[:1], rank=1, world=2)
+    assert [p.name for p in (tmp_path / "r").iterdir()] == ["lookup_00_rank1.npy"]
 
 
 def test_lookup_algorithmic_bytes_brute_force():

@@ -8,7 +8,7 @@ sets=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do sets+=("$1"); shift; done; [
 for i in $(seq 1 $N); do
   for t in "${sets[@]}"; do
     f=gpurun_out/$T/b_${t//[,=]/_}_$i.json
-    timeout -k 10 150 python -u bench.py --no-cpu-baseline --steps 20 --tune "$t" "$@" > "$f" 2>/dev/null || exit 1
+    timeout -k 10 150 python -u bench.py --full --no-cpu-baseline --steps 20 --tune "$t" "$@" > "$f" 2>/dev/null || exit 1
     python -c "import json,sys;d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]);print(sys.argv[2], round(d['ms_per_step'],4), d['lookup_avg_ms'], d['roofline']['frac'])" "$f" "$t"
   done
 done

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One GPU-box session, steps chosen by STEPS (space list, run in order, stop at the first failure):
 #   tests   -m gpu suite (one process) + smoke
-#   bench   bench.py default line (config #3, the BASELINE metric) + the secondary lines in BENCH_SET
+#   bench   bench.py --full default line (config #3, the BASELINE metric) + the secondary lines in BENCH_SET
 #   prof    rocprofv3 --kernel-trace --stats of the default bench line (PROF_ARGS), then of each "name|args" entry
 #           of PROF_SET
 #   pmc     rocprofv3 --pmc passes of the default lookup (tools/pmc_groups.sh; PMC_GROUPS overrides)
@@ -24,7 +24,7 @@ fault() { grep -q "illegal memory access\|hipErrorIllegalAddress\|Memory access 
 
 b() {   # one bench line: name, args...
   local name=$1; shift
-  timeout -k 10 400 python -u bench.py "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"; local rc=$?
+  timeout -k 10 400 python -u bench.py --full "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"; local rc=$?
   echo "bench $name rc=$rc"
   python - "$OUT/$name.json" <<'EOF' 2>/dev/null
 import json, sys

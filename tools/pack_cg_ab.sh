@@ -7,7 +7,7 @@ for i in 1 2; do
   for v in 0 8; do
     for cfg in "shard8|--shard-of 8" "n1|"; do
       name=${cfg%%|*}; args=${cfg#*|}
-      timeout -k 10 300 python -u bench.py --no-cpu-baseline --tune pack_cg=$v $args > $O/${name}_cg${v}_$i.json 2> $O/${name}_cg${v}_$i.err || exit 1
+      timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --tune pack_cg=$v $args > $O/${name}_cg${v}_$i.json 2> $O/${name}_cg${v}_$i.err || exit 1
       python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], sys.argv[3], round(d['ms_per_step'],4), d['build']['avg_ms'])" $O/${name}_cg${v}_$i.json $name cg=$v
     done
   done
