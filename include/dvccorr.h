@@ -81,7 +81,9 @@ typedef enum {
  * makes CorrBlock's matmul and pyramid float16, corr.py:155-167): pack, build (v_mfma_f32_32x32x16_f16),
  * pool, lookup (also convc1-fused) and backward; the on-the-fly entry points (dvc_corr_lookup_fused,
  * dvc_corr_lookup_fused_proj) take it too (round 4): the reference's CorrBlockOnTheFly einsum runs in fp16 under
- * the same autocast (corr_otf.py:198-237), and the window dots are rounded to fp16 like the fp16 pyramid. */
+ * the same autocast (corr_otf.py:198-237), and the window dots are rounded to fp16 like the fp16 pyramid.
+ * DVC_F32 on dvc_corr_lookup_fused_proj (round 7): the reference's fp32 evaluation of CorrBlockOnTheFly
+ * (raft_dvc.py:403-412) with convc1 fused -- fp32 window dots on the matrix cores, the exact split consumer. */
 typedef enum { DVC_F32 = 0, DVC_BF16 = 1, DVC_F16 = 2 } dvc_dtype;
 
 /* Layout flag ORed into the dtype of dvc_pack_targets and the store_dtype of dvc_corr_lookup /
@@ -242,12 +244,15 @@ int dvc_corr_lookup_proj(const void *corr, const float *coords, const void *pack
 
 /* The same composition on the on-the-fly path (CorrBlockOnTheFly.__call__ followed by
  * F.relu(self.convc1(corr)), src/core/corr_otf.py:96-237 + src/core/update.py:246):
- * packed_q / packed_t as for dvc_corr_lookup_fused (bf16 or f16), packed_w from dvc_proj_pack,
- * out (B, 96, Nq) float32.  Queries are processed in order of their level-0 window
+ * packed_q / packed_t as for dvc_corr_lookup_fused (bf16, f16 or f32), packed_w from dvc_proj_pack
+ * (for DVC_F32 from dvc_proj_pack_exact, 2 x dvc_proj_packed_bytes: the bf16 hi block then the lo block, as for
+ * dvc_corr_lookup_proj on an fp32 pyramid), out (B, 96, Nq) float32.  Queries are processed in order of their level-0 window
  * origin (a radix sort per call), so each workgroup's union of windows is small; the
  * per-query 96-channel rows are transposed to (B, 96, Nq) at the end.  Workspace:
  * dvc_lookup_fused_proj_workspace_bytes (sort keys + the [B][Nq][96] rows).
- * Supported: bf16 / f16, radius 1..4, C_pad in {32, 64, 128}, and for the legacy convention
+ * DVC_F32 (k_fused_proj_f32): the window dots are those of dvc_corr_lookup_fused in fp32 (operands split into
+ * three bf16 pieces, fp32 values), convc1 runs on bf16 hi/lo splits of both operands; fp32 tolerance 1e-5.
+ * Supported: bf16 / f16 / f32, radius 1..4, C_pad in {32, 64, 128}, and for the legacy convention
  * W == D at every non-zero level (DVC_ERR_UNSUPPORTED otherwise). */
 size_t dvc_lookup_fused_proj_workspace_bytes(int B, int64_t Nq);
 int dvc_corr_lookup_fused_proj(const void *packed_q, const void *packed_t, const float *coords, const void *packed_w,

@@ -29,8 +29,6 @@
 
 namespace dvc {
 
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-
 template <int R> struct BoxF32Cfg {
     static constexpr int n = 2 * R + 1;
     static constexpr int NW = 2 * R + 2;
@@ -47,32 +45,6 @@ template <int R> struct BoxF32Cfg {
     static_assert(LDS <= 160 * 1024, "LDS");
 };
 
-// 8 fp32 values -> three bf16 pieces, x = x0 + x1 + x2 + O(2^-27 x) (each piece the round-to-nearest-even bf16 of
-// what the previous ones leave)
-struct Split3 {
-    bf16x8 p0, p1, p2;
-};
-__device__ __forceinline__ Split3 split8(const f32x4 &a, const f32x4 &b) {
-    const f32x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    Split3 s;
-    s.p0 = __builtin_convertvector(v, bf16x8);
-    const f32x8 r1 = v - __builtin_convertvector(s.p0, f32x8);
-    s.p1 = __builtin_convertvector(r1, bf16x8);
-    s.p2 = __builtin_convertvector(r1 - __builtin_convertvector(s.p1, f32x8), bf16x8);
-    return s;
-}
-
-// x.y = sum of the piece products down to order 2^-18 (x0 y0; x1 y0, x0 y1; x2 y0, x1 y1, x0 y2), smallest first;
-// what is left out (x2 y1, x1 y2, x2 y2 and the pieces' residuals) is O(2^-26) of |x||y|
-__device__ __forceinline__ f32x4 mma6(const Split3 &a, const Split3 &b, f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p2, b.p0, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p1, b.p1, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p0, b.p2, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p1, b.p0, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p0, b.p1, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p0, b.p0, c, 0, 0, 0);
-}
-
 template <int R, int KS>
 __global__ __launch_bounds__(256, 1) void k_fused_box_f32(const float *__restrict__ Q, const float *__restrict__ Tt,
                                                           LookupArgs A, int Cp, long long t_rows, int Hq, int Wq,
@@ -85,7 +57,7 @@ __global__ __launch_bounds__(256, 1) void k_fused_box_f32(const float *__restric
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    // XCD-aware box order (as k_fused_box): each XCD a contiguous range of boxes in 4 x 4 x 2 groups
+    // XCD-aware box order (as k_fused_box): each XCD a contiguous range of boxes in kBoxGY x kBoxGX x kBoxGZ groups
     constexpr int GY = kBoxGY, GX = kBoxGX, GZ = kBoxGZ;   // (fused_common.h)
     const int nty = (Hq + TY - 1) / TY, ntx = (Wq + TX - 1) / TX, ntz = (Dq + TZ - 1) / TZ;
     const int ngy = (nty + GY - 1) / GY, ngx = (ntx + GX - 1) / GX, ngz = (ntz + GZ - 1) / GZ;

@@ -1,5 +1,5 @@
 // fused_common.h -- wave-uniform helpers shared by the MFMA on-the-fly kernels
-// (fused_box.hip, fused_proj.hip).
+// (fused_box.hip, fused_box_f32.hip, fused_proj.hip, fused_proj_f32.hip).
 #pragma once
 
 #include "common.h"
@@ -9,6 +9,7 @@ namespace dvc {
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ int buni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ long long buni64(long long v) {
@@ -66,5 +67,32 @@ template <int n> struct BRun {
     f32x2 p[n / 2];
     float t;
 };
+
+// fp32 operands on the bf16 matrix cores (k_fused_box_f32, k_fused_proj_f32):
+// 8 fp32 values -> three bf16 pieces, x = x0 + x1 + x2 + O(2^-27 x) (each piece the round-to-nearest-even bf16 of
+// what the previous ones leave)
+struct Split3 {
+    bf16x8 p0, p1, p2;
+};
+__device__ __forceinline__ Split3 split8(const f32x4 &a, const f32x4 &b) {
+    const f32x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+    Split3 s;
+    s.p0 = __builtin_convertvector(v, bf16x8);
+    const f32x8 r1 = v - __builtin_convertvector(s.p0, f32x8);
+    s.p1 = __builtin_convertvector(r1, bf16x8);
+    s.p2 = __builtin_convertvector(r1 - __builtin_convertvector(s.p1, f32x8), bf16x8);
+    return s;
+}
+
+// x.y = sum of the piece products down to order 2^-18 (x0 y0; x1 y0, x0 y1; x2 y0, x1 y1, x0 y2), smallest first;
+// what is left out (x2 y1, x1 y2, x2 y2 and the pieces' residuals) is O(2^-26) of |x||y|
+__device__ __forceinline__ f32x4 mma6(const Split3 &a, const Split3 &b, f32x4 c) {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p2, b.p0, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p1, b.p1, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p0, b.p2, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p1, b.p0, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p0, b.p1, c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p0, b.p0, c, 0, 0, 0);
+}
 
 }  // namespace dvc

@@ -539,15 +539,21 @@ static void launch_fused_proj(const bf16_t *Q, const bf16_t *Tt, const LookupArg
     }
 }
 
+// fp32 blocks (fused_proj_f32.hip)
+void launch_fused_proj_f32(int radius, const float *Q, const float *Tt, const LookupArgs &A,
+                           const unsigned long long *keys, int b, int Cp, long long t_rows, float scale, float *rows,
+                           hipStream_t s);
+
 int fused_lookup_proj(const void *packed_q, const void *packed_t, const float *coords, const void *packed_w,
                       const float *bias, float *out, void *workspace, int B, long long Nq, int C,
                       const dvc_layout &lay, int radius, int convention, int dtype, int ablate, hipStream_t s,
                       char *err, size_t errlen) {
     const int Cp = lay.c_pad;
-    if (dtype != DVC_BF16 && dtype != DVC_F16) {
-        snprintf(err, errlen, "lookup_fused_proj: 16-bit operands only (an fp32 block takes relu(conv3d(lookup)))");
+    if (dtype != DVC_BF16 && dtype != DVC_F16 && dtype != DVC_F32) {
+        snprintf(err, errlen, "lookup_fused_proj: bad dtype %d", dtype);
         return DVC_ERR_UNSUPPORTED;
     }
+    const int es = dtype == DVC_F32 ? 4 : 2;   // bytes per packed operand value
     if (radius < 1 || radius > DVC_PROJ_MAX_RADIUS) {
         snprintf(err, errlen, "lookup_fused_proj: radius %d outside [1, %d]", radius, DVC_PROJ_MAX_RADIUS);
         return DVC_ERR_UNSUPPORTED;
@@ -556,7 +562,7 @@ int fused_lookup_proj(const void *packed_q, const void *packed_t, const float *c
         snprintf(err, errlen, "lookup_fused_proj: C=%d (C_pad %d) not in {32, 64, 128}", C, Cp);
         return DVC_ERR_UNSUPPORTED;
     }
-    if (lay.row_stride * Cp * 2 >= (1LL << 31) - 65536 || Nq >= (1LL << 31)) {
+    if (lay.row_stride * Cp * es >= (1LL << 31) - 65536 || Nq >= (1LL << 31)) {
         snprintf(err, errlen, "lookup_fused_proj: volume too large for 32-bit offsets");
         return DVC_ERR_UNSUPPORTED;
     }
@@ -614,7 +620,10 @@ int fused_lookup_proj(const void *packed_q, const void *packed_t, const float *c
             snprintf(err, errlen, "lookup_fused_proj: radix sort failed");
             return DVC_ERR_RUNTIME;
         }
-        if (dtype == DVC_F16) {
+        if (dtype == DVC_F32) {   // fp32 block: k_fused_proj_f32, packed_w = dvc_proj_pack_exact's hi + lo blocks
+            launch_fused_proj_f32(radius, (const float *)packed_q, (const float *)packed_t, A, kout, b, Cp,
+                                  lay.row_stride, scale, rows, s);
+        } else if (dtype == DVC_F16) {
             switch (radius) {
             case 1: launch_fused_proj<1, f16_t>(Q, Tt, A, kout, b, Cp, lay.row_stride, scale, rows, s); break;
             case 2: launch_fused_proj<2, f16_t>(Q, Tt, A, kout, b, Cp, lay.row_stride, scale, rows, s); break;

@@ -120,11 +120,12 @@ class _Block:
 
     def _convc1_fusable(self, weight: torch.Tensor, bias: torch.Tensor, w: torch.Tensor) -> bool:
         """The fused convc1 kernels cover radius 1..4, 96 output channels and no legacy level with W != D: a bf16 /
-        fp16 block with fp16 MFMA operands, and (round 5, materialised blocks only) an fp32 block through the exact
-        split consumer (bf16 hi/lo operands, fp32 tolerance; the reference's fp32 evaluation path,
-        evaluate_phase1.py:115-131).  The on-the-fly fp32 block keeps the composition.  With gradients (the
-        Trainer's path, trainer.py:249-257) the fused kernel runs as dvccorr::lookup_convc1_ad (_convc1_grad)."""
-        return ((self.precision in ("bf16", "fp16") or (self.precision == "fp32" and isinstance(self, CorrBlock)))
+        fp16 block with fp16 MFMA operands, and an fp32 block through the exact split consumer (bf16 hi/lo operands,
+        fp32 tolerance; the reference's fp32 evaluation path, evaluate_phase1.py:115-131) -- materialised since
+        round 5 (k_lookup_tile<PROJ = 2>), on the fly since round 7 (k_fused_proj_f32).  With gradients (the
+        Trainer's path, trainer.py:249-257) the fused kernel runs as dvccorr::lookup_convc1_ad (_convc1_grad), except
+        for an fp32 on-the-fly block, which keeps the composition under autograd."""
+        return (self.precision in ("bf16", "fp16", "fp32")
                 and 1 <= self.radius <= ops._lib.PROJ_MAX_RADIUS and w.shape[0] == ops._lib.PROJ_COUT
                 and not (self.legacy_wd_swap and any(lw != ld and min(lh, lw, ld) > 1
                                                      for lh, lw, ld in self._lay.levels())))
@@ -321,15 +322,20 @@ class CorrBlockFused(_Block):
     def lookup_convc1(self, coords: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
         """F.relu(convc1(self(coords))) -> (B, 96, H, W, D) fp32 with convc1 fused into the on-the-fly lookup
         (dvc_corr_lookup_fused_proj): the L*(2r+1)^3 channels never reach HBM, and the queries are grouped by
-        window position so each workgroup's window union is small.  Same numerics and fallbacks as
-        CorrBlock.lookup_convc1 (fp16 convc1 operands, tolerance 1e-2; fp32 blocks, gradients, radii > 4,
-        legacy W != D levels and C_pad outside {32, 64, 128} take relu(conv3d(self(coords))))."""
+        window position so each workgroup's window union is small.  Same numerics as CorrBlock.lookup_convc1:
+        fp16 convc1 operands for a bf16 / fp16 block (tolerance 1e-2); an fp32 block (k_fused_proj_f32) keeps its
+        window dots in fp32 and splits the convc1 operands into bf16 hi + lo (tolerance 1e-5).  Radii > 4, legacy
+        W != D levels, C_pad outside {32, 64, 128} and an fp32 block under autograd take
+        relu(conv3d(self(coords)))."""
         self._check_coords(coords)
         B, C, H, W, D = self.shape
         w = weight.reshape(weight.shape[0], -1)
         if not (self._convc1_fusable(weight, bias, w) and self._lay.c_pad in (32, 64, 128)):
             return self._convc1_composition(coords, w, bias)
-        packed = ops.proj_pack_cached(weight, self.num_levels, self.radius, self.legacy_wd_swap)
+        fp32 = self.precision == "fp32"
+        if fp32 and self._convc1_grad(weight, bias):   # (no fp32 on-the-fly lookup_convc1_ad)
+            return self._convc1_composition(coords, w, bias)
+        packed = ops.proj_pack_cached(weight, self.num_levels, self.radius, self.legacy_wd_swap, exact=fp32)
         if self._convc1_grad(weight, bias):
             return self._convc1_ad(coords, weight, bias, packed, None)
         out = library.lookup_fused_proj(self._q, self._t, coords.reshape(B, 3, H * W * D), packed, bias, C, H, W,

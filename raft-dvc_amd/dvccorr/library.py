@@ -7,6 +7,7 @@ the PyTorch dispatcher as named operators with shape functions:
     dvccorr::lookup(corr, coords, ...)           -> (B, L*(2r+1)^3, Nq) f32            corr.py:169-208
     dvccorr::lookup_fused(q, t, coords, ...)     -> (B, L*(2r+1)^3, Nq) f32            corr_otf.py:96-237
     dvccorr::lookup_fused_proj(q, t, coords, w, b, ...) -> (B, 96, Nq) f32 = relu(convc1(lookup_fused))
+                                                 (bf16 / fp16 operands, or fp32 with the exact hi / lo weight pack)
                                                                                        + update.py:246
     dvccorr::corr_backward(q, t, coords, g, ...) -> (d fmap1 (B, C, Nq), d fmap2)      autograd of corr.py:141-208
     dvccorr::lookup_convc1_ad(fmap1, fmap2, weight, bias, corr?, q, t, coords, packed_w, ...)

@@ -267,7 +267,8 @@ def lookup_fused_proj(packed_q: torch.Tensor, packed_t: torch.Tensor, coords: to
                       bias: torch.Tensor, C: int, H: int, W: int, D: int, num_levels: int, radius: int, legacy: bool,
                       dtype: int, out: torch.Tensor = None, workspace: torch.Tensor = None) -> torch.Tensor:
     """relu(convc1(lookup_fused(coords))) -> (B, 96, Nq) f32 on the on-the-fly path, the lookup never written
-    (dvc_corr_lookup_fused_proj: queries grouped by window origin, convc1 on MFMA)."""
+    (dvc_corr_lookup_fused_proj: queries grouped by window origin, convc1 on MFMA).  fp32 operands (DVC_F32) run
+    k_fused_proj_f32, whose exact split consumer reads proj_pack(..., exact=True)'s hi + lo blocks."""
     _need_cuda(packed_q, packed_t, coords, packed_w, bias)
     _expect_layout(packed_t, dtype, "corr_lookup_fused_proj")
     B, Nq, _ = packed_q.shape
@@ -275,6 +276,11 @@ def lookup_fused_proj(packed_q: torch.Tensor, packed_t: torch.Tensor, coords: to
     b = _f32c(bias)
     if b.numel() != _lib.PROJ_COUT:
         raise ValueError(f"convc1 bias must have {_lib.PROJ_COUT} entries; got {b.numel()}")
+    need = lib().dvc_proj_packed_bytes(num_levels, radius) * (2 if int(dtype) == DVC_F32 else 1)
+    have = packed_w.numel() * packed_w.element_size()
+    if have < need:
+        raise ValueError(f"lookup_fused_proj: packed_w holds {have} bytes; this dtype's consumer reads {need} "
+                         f"(fp32 blocks take proj_pack(..., exact=True); include/dvccorr.h, ABI 3)")
     if out is None:
         out = torch.empty((B, _lib.PROJ_COUT, Nq), dtype=torch.float32, device=packed_q.device)
     nws = lib().dvc_lookup_fused_proj_workspace_bytes(B, Nq)

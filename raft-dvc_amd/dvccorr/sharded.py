@@ -149,19 +149,22 @@ class HipRows:
 
     def lookup_convc1(self, coords_flat: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
         """relu(convc1(lookup)) of this rank's rows, convc1 fused into the lookup kernel (materialised:
-        dvc_corr_lookup_proj, fused: dvc_corr_lookup_fused_proj) for a bf16 block; an fp32 block, or shapes
-        the fused kernels do not cover, take relu(W . lookup + b) in fp32."""
+        dvc_corr_lookup_proj, fused: dvc_corr_lookup_fused_proj) for a bf16 / fp16 block and for an fp32 on-the-fly
+        block (exact hi / lo pack); a materialised fp32 block, or shapes the fused kernels do not cover, take
+        relu(W . lookup + b) in fp32."""
         C, H, W, D = self.dims
         w = weight.reshape(weight.shape[0], -1)
         generic = self.legacy and any(lw != ld and min(lh, lw, ld) > 1
                                       for lh, lw, ld in layout(H, W, D, self.L, C).levels())
-        fusable = (self.dt in (ops.dtype_code("bf16"), ops.dtype_code("fp16")) and 1 <= self.R <= ops._lib.PROJ_MAX_RADIUS
+        fp32 = self.dt == ops.dtype_code("fp32")
+        fusable = ((self.dt in (ops.dtype_code("bf16"), ops.dtype_code("fp16")) or (fp32 and self.impl == "fused"))
+                   and 1 <= self.R <= ops._lib.PROJ_MAX_RADIUS
                    and w.shape[0] == ops._lib.PROJ_COUT and not generic
                    and (self.impl == "materialised" or layout(H, W, D, self.L, C).c_pad in (32, 64, 128)))
         if not fusable:
             out = self.lookup(coords_flat)
             return torch.relu(torch.matmul(w.float(), out) + bias.float().view(1, -1, 1))
-        packed = ops.proj_pack_cached(weight, self.L, self.R, self.legacy)
+        packed = ops.proj_pack_cached(weight, self.L, self.R, self.legacy, exact=fp32)
         if self.impl == "materialised":
             return ops.lookup_proj(self.corr, coords_flat, packed, bias, H, W, D, self.L, self.R, self.legacy,
                                    self.ldt)
