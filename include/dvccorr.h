@@ -278,6 +278,33 @@ int dvc_upflow(const float *flow, float *flow_up, int B, int C, int h, int w, in
 int dvc_flow_step(const float *coords1, const float *delta_flow, float *coords1_out, float *flow_up, int B, int h,
                   int w, int d, int H, int W, int D, void *stream);
 
+/* SepConvGRU3D forward, one fused launch per axis pass (src/core/update.py:139-199; the update block's default
+ * GRU, hidden 96 and input 147 at update.py:283-297).  Per axis a in (h, w, d), conv_*_a a 5-tap 1-D convolution
+ * zero-padded by 2 along a:  z = sigmoid(conv_z(cat[h, x])), r = sigmoid(conv_r(cat[h, x])),
+ * q = tanh(conv_q(cat[r h, x])), h_out = (1 - z) h + z q.  Tensors are (B, C, H, W, D) float32, contiguous.
+ *   dvc_gru_packed_bytes  bytes of one axis's packed weights and biases (0 for an unsupported shape or dtype)
+ *   dvc_gru_pack          packs one axis: wz, wr, wq the (hidden, hidden + input, 5) float32 weights of the
+ *                         axis's three convolutions (their contiguous storage), bz, br, bq the (hidden) biases,
+ *                         into the MFMA operand order [gate][tap][c_in] padded.  dtype DVC_BF16 / DVC_F16:
+ *                         one 16-bit block; DVC_F32: bf16 hi and lo pieces (three products per step, fp32
+ *                         tolerance 1e-5; the 16-bit dtypes 1e-2).  A packed buffer is used with the dtype
+ *                         it was packed for.
+ *   dvc_sep_gru_pass      one axis pass (axis 0 = h, 1 = w, 2 = d) with that axis's packed buffer; h_out must
+ *                         not overlap h or x (a pass reads its neighbours).  No atomics, no allocation, no
+ *                         host synchronisation: capturable in a graph.  Workgroups own DVC_GRU_SEG output
+ *                         positions along the axis.
+ * Errors, before any GPU call: a null pointer, B / H / W / D < 1, axis outside 0..2, a bad dtype or overlapping
+ * buffers are DVC_ERR_INVALID; hidden != DVC_GRU_HIDDEN, input outside 1..DVC_GRU_MAX_INPUT or a volume of
+ * 2^31 voxels or more are DVC_ERR_UNSUPPORTED. */
+#define DVC_GRU_HIDDEN 96
+#define DVC_GRU_MAX_INPUT 160
+#define DVC_GRU_SEG 8
+size_t dvc_gru_packed_bytes(int hidden, int input, int dtype);
+int dvc_gru_pack(const float *wz, const float *wr, const float *wq, const float *bz, const float *br,
+                 const float *bq, void *packed, int hidden, int input, int dtype, void *stream);
+int dvc_sep_gru_pass(const float *h, const float *x, const void *packed, float *h_out, int B, int hidden, int input,
+                     int H, int W, int D, int axis, int dtype, void *stream);
+
 /* Diagnostics hook for A/B timing.  The product kernel selection is a fixed table;
  * an override set here is PROCESS-GLOBAL (round 6; it was thread-local, which a
  * backward run on the autograd engine's worker thread never saw): it changes every

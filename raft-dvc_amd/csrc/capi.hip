@@ -70,6 +70,11 @@ __global__ void k_coords_grid(float *, long long, int, int, int);
 template <bool DELTA, bool SUBGRID, int VEC, bool STAGED>
 __global__ void k_upflow(const float *, const float *, float *, float *, long long, int, int, int, int, int, int, int,
                          float, float, float, float, float, float, int, int, int);
+size_t gru_packed_bytes(int dtype);
+hipError_t launch_gru_pack(const float *wz, const float *wr, const float *wq, const float *bz, const float *br,
+                           const float *bq, void *packed, int Cx, int dtype, hipStream_t s);
+hipError_t launch_sep_gru_pass(const float *h, const float *x, const void *packed, float *h_out, int B, int Cx, int H,
+                               int W, int D, int axis, int dtype, hipStream_t s);
 }  // namespace dvc
 
 using namespace dvc;
@@ -1151,6 +1156,47 @@ int dvc_flow_step(const float *coords1, const float *delta_flow, float *coords1_
                   int w, int d, int H, int W, int D, void *stream) {
     return launch_upflow(coords1, delta_flow, coords1_out, flow_up, B, 3, h, w, d, H, W, D, true, stream,
                          "flow_step");
+}
+
+// SepConvGRU3D forward (gru.hip): the shapes k_sep_gru_pass covers
+static int gru_shape_check(const char *what, int hidden, int input, int dtype) {
+    if (dtype != DVC_BF16 && dtype != DVC_F32 && dtype != DVC_F16)
+        return fail(DVC_ERR_INVALID, "%s: bad dtype %d", what, dtype);
+    if (hidden != DVC_GRU_HIDDEN || input < 1 || input > DVC_GRU_MAX_INPUT)
+        return fail(DVC_ERR_UNSUPPORTED, "%s: hidden=%d input=%d (the kernel covers hidden %d, input 1..%d)", what,
+                    hidden, input, DVC_GRU_HIDDEN, DVC_GRU_MAX_INPUT);
+    return DVC_OK;
+}
+
+size_t dvc_gru_packed_bytes(int hidden, int input, int dtype) {
+    if (gru_shape_check("gru_packed_bytes", hidden, input, dtype)) return 0;
+    return gru_packed_bytes(dtype);
+}
+
+int dvc_gru_pack(const float *wz, const float *wr, const float *wq, const float *bz, const float *br,
+                 const float *bq, void *packed, int hidden, int input, int dtype, void *stream) {
+    if (!wz || !wr || !wq || !bz || !br || !bq || !packed) return fail(DVC_ERR_INVALID, "gru_pack: null pointer");
+    if (int rc = gru_shape_check("gru_pack", hidden, input, dtype)) return rc;
+    hipError_t e = launch_gru_pack(wz, wr, wq, bz, br, bq, packed, input, dtype, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(DVC_ERR_LAUNCH, "gru_pack: %s", hipGetErrorString(e));
+    return DVC_OK;
+}
+
+int dvc_sep_gru_pass(const float *h, const float *x, const void *packed, float *h_out, int B, int hidden, int input,
+                     int H, int W, int D, int axis, int dtype, void *stream) {
+    if (!h || !x || !packed || !h_out) return fail(DVC_ERR_INVALID, "sep_gru_pass: null pointer");
+    if (B < 1 || H < 1 || W < 1 || D < 1)
+        return fail(DVC_ERR_INVALID, "sep_gru_pass: B=%d volume (%d,%d,%d)", B, H, W, D);
+    if (axis < 0 || axis > 2) return fail(DVC_ERR_INVALID, "sep_gru_pass: axis %d is not 0 (h), 1 (w) or 2 (d)", axis);
+    if (int rc = gru_shape_check("sep_gru_pass", hidden, input, dtype)) return rc;
+    const long long vox = (long long)B * H * W * D;
+    if (vox >= (1LL << 31)) return fail(DVC_ERR_UNSUPPORTED, "sep_gru_pass: %lld voxels exceed 32-bit line indices", vox);
+    const size_t hb = (size_t)vox * hidden * 4, xb = (size_t)vox * input * 4;
+    if (overlaps(h_out, hb, h, hb) || overlaps(h_out, hb, x, xb))
+        return fail(DVC_ERR_INVALID, "sep_gru_pass: h_out must not overlap h or x (a pass reads its neighbours)");
+    hipError_t e = launch_sep_gru_pass(h, x, packed, h_out, B, input, H, W, D, axis, dtype, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(DVC_ERR_LAUNCH, "sep_gru_pass: %s", hipGetErrorString(e));
+    return DVC_OK;
 }
 
 }  // extern "C"

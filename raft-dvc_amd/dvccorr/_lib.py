@@ -30,9 +30,13 @@ EXPORTED = (
     "dvc_proj_packed_bytes", "dvc_proj_pack", "dvc_proj_pack_exact",
     "dvc_corr_lookup_proj", "dvc_lookup_fused_proj_workspace_bytes", "dvc_corr_lookup_fused_proj",
     "dvc_coords_grid", "dvc_upflow", "dvc_flow_step", "dvc_bricked_levels", "dvc_corr_backward_mfma", "dvc_corr_backward_gout64",
+    "dvc_gru_packed_bytes", "dvc_gru_pack", "dvc_sep_gru_pass",
 )
 PROJ_COUT = 96          # DVC_PROJ_COUT (convc1 output channels, update.py:222)
 PROJ_MAX_RADIUS = 4     # DVC_PROJ_MAX_RADIUS
+GRU_HIDDEN = 96         # DVC_GRU_HIDDEN (SepConvGRU3D hidden channels the kernel covers, update.py:283-297)
+GRU_MAX_INPUT = 160     # DVC_GRU_MAX_INPUT
+GRU_SEG = 8             # DVC_GRU_SEG: output positions along the conv axis per workgroup of k_sep_gru_pass
 
 
 class Layout(ctypes.Structure):
@@ -101,6 +105,9 @@ def lib() -> ctypes.CDLL:
         "dvc_coords_grid": (i32, [vp, i32, i32, i32, i32, vp]),
         "dvc_upflow": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "dvc_flow_step": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "dvc_gru_packed_bytes": (sz, [i32, i32, i32]),
+        "dvc_gru_pack": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+        "dvc_sep_gru_pass": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "dvc_set_tuning": (i32, [ctypes.c_char_p, i32]),
         "dvc_last_error": (ctypes.c_char_p, []),
         "dvc_version": (ctypes.c_char_p, []),

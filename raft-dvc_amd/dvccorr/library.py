@@ -19,6 +19,9 @@ the PyTorch dispatcher as named operators with shape functions:
         registered autograd formula is dvccorr::corr_backward.  Coordinates get no
         gradient (RAFTDVC.forward detaches them, raft_dvc.py:441).
 
+    dvccorr::sep_gru(h, x, packed, dtype)        -> h after SepConvGRU3D's three passes  update.py:178-199
+                                                 (forward only: no autograd formula is registered)
+
 Every op runs the HIP kernels of libdvccorr.so through ops.py (no CPU
 fallback); the fake (meta) implementations only compute output shapes, so the
 ops trace under torch.compile / FakeTensorMode and torch.library.opcheck.
@@ -198,4 +201,14 @@ def _lookup_convc1_backward(ctx, grad_out):
 torch.library.register_autograd("dvccorr::lookup_convc1_ad", _lookup_convc1_backward,
                                 setup_context=_lookup_convc1_setup)
 
-__all__ = ["build", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "lookup_ad", "lookup_convc1_ad"]
+@torch.library.custom_op("dvccorr::sep_gru", mutates_args=())
+def sep_gru(h: Tensor, x: Tensor, packed: Tensor, dtype: int) -> Tensor:
+    return ops.sep_gru(h, x, packed, dtype)
+
+
+@sep_gru.register_fake
+def _(h, x, packed, dtype):
+    return h.new_empty(h.shape, dtype=_F32)
+
+
+__all__ = ["sep_gru", "build", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "lookup_ad", "lookup_convc1_ad"]

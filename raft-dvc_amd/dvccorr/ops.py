@@ -15,6 +15,8 @@ straight to libdvccorr.so (no CPU fallback).  Shapes follow include/dvccorr.h:
     coords_grid(B, H, W, D, device)                    -> (B, 3, H, W, D)      f32
     upflow(flow (B, C, h, w, d), (H, W, D))            -> (B, C, H, W, D)      f32
     flow_step(coords1, delta (B, 3, h, w, d), (H,W,D)) -> coords1 + delta, upflow(coords1 + delta - coords0)
+    gru_pack(18 SepConvGRU3D tensors, dtype)           -> packed weights of the three axis passes
+    sep_gru(h (B, 96, H, W, D), x (B, Ci, H, W, D), packed, dtype) -> h after the h, w and d passes  f32
 """
 from __future__ import annotations
 
@@ -399,3 +401,54 @@ __all__ = ["pack_queries", "pack_targets", "pack_targets_gathered", "build", "po
            "proj_pack", "proj_pack_cached", "lookup_proj",
            "coords_grid", "upflow", "flow_step",
            "fused_workspace", "dtype_code", "layout", "bricked_levels", "DVC_BRICKED", "_lib"]
+
+
+_GRU_AXES = ("h", "w", "d")
+
+
+@_on_device
+def gru_pack(weights, dtype: int) -> torch.Tensor:
+    """The eighteen SepConvGRU3D tensors (state_dict names conv{z,r,q}_{h,w,d}.{weight,bias}) -> one buffer of the
+    three axes' packed MFMA operands and biases (dvc_gru_pack; 3 x dvc_gru_packed_bytes)."""
+    wz = weights["convz_h.weight"]
+    _need_cuda(wz)
+    hidden, cin = int(wz.shape[0]), int(wz.shape[1])
+    nbytes = lib().dvc_gru_packed_bytes(hidden, cin - hidden, dtype)
+    if nbytes == 0:
+        raise NotImplementedError(f"gru_pack: hidden={hidden} input={cin - hidden} is outside the kernel's shapes "
+                                  f"(hidden {_lib.GRU_HIDDEN}, input 1..{_lib.GRU_MAX_INPUT})")
+    out = torch.empty((3, nbytes // 4), dtype=torch.float32, device=wz.device)
+    for a, ax in enumerate(_GRU_AXES):
+        ws = [_f32c(weights[f"conv{g}_{ax}.weight"].detach().reshape(hidden, cin, 5)) for g in "zrq"]
+        bs = [_f32c(weights[f"conv{g}_{ax}.bias"].detach()) for g in "zrq"]
+        check(lib().dvc_gru_pack(*map(_ptr, ws + bs), _ptr(out[a]), hidden, cin - hidden, dtype, _stream(wz)),
+              "gru_pack")
+    return out
+
+
+@_on_device
+def sep_gru_pass(h: torch.Tensor, x: torch.Tensor, packed_axis: torch.Tensor, out: torch.Tensor, axis: int,
+                 dtype: int) -> torch.Tensor:
+    """One axis pass (dvc_sep_gru_pass): h, x, out contiguous float32, out not overlapping h."""
+    _need_cuda(h, x, packed_axis, out)
+    B, hidden, H, W, D = h.shape
+    check(lib().dvc_sep_gru_pass(_ptr(h), _ptr(x), _ptr(packed_axis), _ptr(out), B, hidden, x.shape[1], H, W, D, axis,
+                                 dtype, _stream(h)), "sep_gru_pass")
+    return out
+
+
+@_on_device
+def sep_gru(h: torch.Tensor, x: torch.Tensor, packed: torch.Tensor, dtype: int) -> torch.Tensor:
+    """SepConvGRU3D.forward (update.py:178-199): the h, w and d passes, ping-ponged between two new buffers (the
+    caller's h is only read)."""
+    _need_cuda(h, x, packed)
+    h, x = _f32c(h), _f32c(x)
+    need = 3 * lib().dvc_gru_packed_bytes(h.shape[1], x.shape[1], dtype)
+    if need == 0 or packed.numel() * packed.element_size() != need:
+        raise ValueError(f"sep_gru: packed weights of {packed.numel() * packed.element_size()} bytes; hidden "
+                         f"{h.shape[1]}, input {x.shape[1]} and this precision take {need} (gru_pack with the same dtype)")
+    a, b = torch.empty_like(h), torch.empty_like(h)
+    sep_gru_pass(h, x, packed[0], a, 0, dtype)
+    sep_gru_pass(a, x, packed[1], b, 1, dtype)
+    sep_gru_pass(b, x, packed[2], a, 2, dtype)
+    return a
