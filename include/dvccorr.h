@@ -305,6 +305,43 @@ int dvc_gru_pack(const float *wz, const float *wr, const float *wq, const float 
 int dvc_sep_gru_pass(const float *h, const float *x, const void *packed, float *h_out, int B, int hidden, int input,
                      int H, int W, int D, int axis, int dtype, void *stream);
 
+/* The update block's plain convolutions on the matrix cores (src/core/update.py:205-348: BasicMotionEncoder's
+ * convf1 / convf2 / conv and the flow and uncertainty heads).  Tensors are (B, C, H, W, D) float32, contiguous.
+ *   dvc_conv3   3 x 3 x 3, zero padding 1, stride 1, + bias, + ReLU when relu != 0.  The input is the channel
+ *               concatenation of src0 (c0 channels) and src1 (c1 channels; src1 may be NULL, c1 is then ignored);
+ *               the output is the channel slice [dst_offset, dst_offset + cout) of dst, a tensor with dst_channels
+ *               channels.  dst must not overlap a source.  Workgroups own boxes of
+ *               DVC_CONV3_TH x DVC_CONV3_TW x DVC_CONV3_TD output voxels.
+ *   dvc_conv3_pack / dvc_conv3_packed_bytes   w the (cout, cin, 3, 3, 3) float32 weight, bias (cout), into 1 KB MFMA
+ *               A-operand fragments [32-channel chunk][tap][16-channel tile] (x 2 pieces, bf16 hi and lo, for
+ *               DVC_F32), then 16 float32 biases per tile.  The tile count is cout / 16 rounded up to 1, 2, 4, 5 or
+ *               8 (zero rows; padded outputs are never stored).
+ *   dvc_conv7_flow (+ _pack, _packed_bytes)   encoder.convf1: 3 -> DVC_CONV7_COUT channels, 7 x 7 x 7, zero padding
+ *               3, + bias + ReLU; w (64, 3, 7, 7, 7), fragments [kh][kw][tile] with k = 8 ci + kd.
+ * dtype as the GRU: DVC_BF16 / DVC_F16 round the operands once (tolerance 1e-2), DVC_F32 uses bf16 hi + lo pieces
+ * (1e-5); accumulation and output are float32.  No atomics, no allocation, no host synchronisation.
+ * Errors, before any GPU call: a null pointer, B / H / W / D < 1, a bad dtype, c0 / c1 / cout < 1,
+ * dst_offset < 0 or dst_offset + cout > dst_channels, or dst overlapping a source are DVC_ERR_INVALID; c0 + c1 >
+ * DVC_CONV3_MAX_CIN, cout > DVC_CONV3_MAX_COUT or 2^31 voxels or more are DVC_ERR_UNSUPPORTED
+ * (dvc_conv3_packed_bytes returns 0 for both). */
+#define DVC_CONV3_TH 4
+#define DVC_CONV3_TW 4
+#define DVC_CONV3_TD 16
+#define DVC_CONV3_MAX_CIN 128
+#define DVC_CONV3_MAX_COUT 128
+#define DVC_CONV7_TH 4
+#define DVC_CONV7_TW 4
+#define DVC_CONV7_TD 16
+#define DVC_CONV7_COUT 64
+size_t dvc_conv3_packed_bytes(int cin, int cout, int dtype);
+int dvc_conv3_pack(const float *w, const float *bias, void *packed, int cin, int cout, int dtype, void *stream);
+int dvc_conv3(const float *src0, int c0, const float *src1, int c1, const void *packed, float *dst, int dst_channels,
+              int dst_offset, int cout, int relu, int B, int H, int W, int D, int dtype, void *stream);
+size_t dvc_conv7_flow_packed_bytes(int dtype);
+int dvc_conv7_flow_pack(const float *w, const float *bias, void *packed, int dtype, void *stream);
+int dvc_conv7_flow(const float *flow, const void *packed, float *dst, int B, int H, int W, int D, int dtype,
+                   void *stream);
+
 /* Diagnostics hook for A/B timing.  The product kernel selection is a fixed table;
  * an override set here is PROCESS-GLOBAL (round 6; it was thread-local, which a
  * backward run on the autograd engine's worker thread never saw): it changes every

@@ -75,6 +75,16 @@ hipError_t launch_gru_pack(const float *wz, const float *wr, const float *wq, co
                            const float *bq, void *packed, int Cx, int dtype, hipStream_t s);
 hipError_t launch_sep_gru_pass(const float *h, const float *x, const void *packed, float *h_out, int B, int Cx, int H,
                                int W, int D, int axis, int dtype, hipStream_t s);
+size_t conv3_packed_bytes(int cin, int cout, int dtype);
+hipError_t launch_conv3_pack(const float *w, const float *bias, void *packed, int cin, int cout, int dtype,
+                             hipStream_t s);
+hipError_t launch_conv3(const float *src0, int c0, const float *src1, int c1, const void *packed, float *dst,
+                        int dst_channels, int dst_offset, int cout, int relu, int B, int H, int W, int D, int dtype,
+                        hipStream_t s);
+size_t conv7_packed_bytes(int dtype);
+hipError_t launch_conv7_pack(const float *w, const float *bias, void *packed, int dtype, hipStream_t s);
+hipError_t launch_conv7_flow(const float *flow, const void *packed, float *dst, int B, int H, int W, int D, int dtype,
+                             hipStream_t s);
 }  // namespace dvc
 
 using namespace dvc;
@@ -1196,6 +1206,84 @@ int dvc_sep_gru_pass(const float *h, const float *x, const void *packed, float *
         return fail(DVC_ERR_INVALID, "sep_gru_pass: h_out must not overlap h or x (a pass reads its neighbours)");
     hipError_t e = launch_sep_gru_pass(h, x, packed, h_out, B, input, H, W, D, axis, dtype, (hipStream_t)stream);
     if (e != hipSuccess) return fail(DVC_ERR_LAUNCH, "sep_gru_pass: %s", hipGetErrorString(e));
+    return DVC_OK;
+}
+
+// the update block's plain convolutions (conv3.hip): the shapes k_conv3_mfma covers
+static int conv3_shape_check(const char *what, int cin, int cout, int dtype) {
+    if (dtype != DVC_BF16 && dtype != DVC_F32 && dtype != DVC_F16)
+        return fail(DVC_ERR_INVALID, "%s: bad dtype %d", what, dtype);
+    if (cin < 1 || cout < 1) return fail(DVC_ERR_INVALID, "%s: cin=%d cout=%d", what, cin, cout);
+    if (cin > DVC_CONV3_MAX_CIN || cout > DVC_CONV3_MAX_COUT)
+        return fail(DVC_ERR_UNSUPPORTED, "%s: cin=%d cout=%d (the kernel covers cin 1..%d, cout 1..%d)", what, cin,
+                    cout, DVC_CONV3_MAX_CIN, DVC_CONV3_MAX_COUT);
+    return DVC_OK;
+}
+
+size_t dvc_conv3_packed_bytes(int cin, int cout, int dtype) {
+    if (conv3_shape_check("conv3_packed_bytes", cin, cout, dtype)) return 0;
+    return conv3_packed_bytes(cin, cout, dtype);
+}
+
+int dvc_conv3_pack(const float *w, const float *bias, void *packed, int cin, int cout, int dtype, void *stream) {
+    if (!w || !bias || !packed) return fail(DVC_ERR_INVALID, "conv3_pack: null pointer");
+    if (int rc = conv3_shape_check("conv3_pack", cin, cout, dtype)) return rc;
+    hipError_t e = launch_conv3_pack(w, bias, packed, cin, cout, dtype, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(DVC_ERR_LAUNCH, "conv3_pack: %s", hipGetErrorString(e));
+    return DVC_OK;
+}
+
+int dvc_conv3(const float *src0, int c0, const float *src1, int c1, const void *packed, float *dst, int dst_channels,
+              int dst_offset, int cout, int relu, int B, int H, int W, int D, int dtype, void *stream) {
+    if (!src0 || !packed || !dst) return fail(DVC_ERR_INVALID, "conv3: null pointer");
+    if (B < 1 || H < 1 || W < 1 || D < 1) return fail(DVC_ERR_INVALID, "conv3: B=%d volume (%d,%d,%d)", B, H, W, D);
+    if (!src1) c1 = 0;
+    if (c0 < 1 || c1 < 0 || (src1 && c1 < 1)) return fail(DVC_ERR_INVALID, "conv3: c0=%d c1=%d", c0, c1);
+    if (c0 > DVC_CONV3_MAX_CIN || c1 > DVC_CONV3_MAX_CIN)
+        return fail(DVC_ERR_UNSUPPORTED, "conv3: c0=%d c1=%d (the kernel covers c0 + c1 <= %d)", c0, c1,
+                    DVC_CONV3_MAX_CIN);
+    if (int rc = conv3_shape_check("conv3", c0 + c1, cout, dtype)) return rc;
+    if (dst_offset < 0 || dst_channels < 1 || dst_offset > dst_channels - cout)
+        return fail(DVC_ERR_INVALID, "conv3: channels [%d, %d + %d) are not inside dst's %d", dst_offset, dst_offset,
+                    cout, dst_channels);
+    const long long vox = (long long)B * H * W * D;
+    if (vox >= (1LL << 31)) return fail(DVC_ERR_UNSUPPORTED, "conv3: %lld voxels exceed 32-bit indices", vox);
+    const size_t db = (size_t)vox * dst_channels * 4;
+    if (overlaps(dst, db, src0, (size_t)vox * c0 * 4) || (src1 && overlaps(dst, db, src1, (size_t)vox * c1 * 4)))
+        return fail(DVC_ERR_INVALID, "conv3: dst must not overlap a source (a voxel reads its neighbours)");
+    hipError_t e = launch_conv3(src0, c0, src1, c1, packed, dst, dst_channels, dst_offset, cout, relu != 0, B, H, W, D,
+                                dtype, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(DVC_ERR_LAUNCH, "conv3: %s", hipGetErrorString(e));
+    return DVC_OK;
+}
+
+size_t dvc_conv7_flow_packed_bytes(int dtype) {
+    if (dtype != DVC_BF16 && dtype != DVC_F32 && dtype != DVC_F16) return 0;
+    return conv7_packed_bytes(dtype);
+}
+
+int dvc_conv7_flow_pack(const float *w, const float *bias, void *packed, int dtype, void *stream) {
+    if (!w || !bias || !packed) return fail(DVC_ERR_INVALID, "conv7_flow_pack: null pointer");
+    if (dtype != DVC_BF16 && dtype != DVC_F32 && dtype != DVC_F16)
+        return fail(DVC_ERR_INVALID, "conv7_flow_pack: bad dtype %d", dtype);
+    hipError_t e = launch_conv7_pack(w, bias, packed, dtype, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(DVC_ERR_LAUNCH, "conv7_flow_pack: %s", hipGetErrorString(e));
+    return DVC_OK;
+}
+
+int dvc_conv7_flow(const float *flow, const void *packed, float *dst, int B, int H, int W, int D, int dtype,
+                   void *stream) {
+    if (!flow || !packed || !dst) return fail(DVC_ERR_INVALID, "conv7_flow: null pointer");
+    if (B < 1 || H < 1 || W < 1 || D < 1)
+        return fail(DVC_ERR_INVALID, "conv7_flow: B=%d volume (%d,%d,%d)", B, H, W, D);
+    if (dtype != DVC_BF16 && dtype != DVC_F32 && dtype != DVC_F16)
+        return fail(DVC_ERR_INVALID, "conv7_flow: bad dtype %d", dtype);
+    const long long vox = (long long)B * H * W * D;
+    if (vox >= (1LL << 31)) return fail(DVC_ERR_UNSUPPORTED, "conv7_flow: %lld voxels exceed 32-bit indices", vox);
+    if (overlaps(dst, (size_t)vox * DVC_CONV7_COUT * 4, flow, (size_t)vox * 3 * 4))
+        return fail(DVC_ERR_INVALID, "conv7_flow: dst must not overlap flow (a voxel reads its neighbours)");
+    hipError_t e = launch_conv7_flow(flow, packed, dst, B, H, W, D, dtype, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(DVC_ERR_LAUNCH, "conv7_flow: %s", hipGetErrorString(e));
     return DVC_OK;
 }
 

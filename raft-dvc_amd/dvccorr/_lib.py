@@ -31,12 +31,19 @@ EXPORTED = (
     "dvc_corr_lookup_proj", "dvc_lookup_fused_proj_workspace_bytes", "dvc_corr_lookup_fused_proj",
     "dvc_coords_grid", "dvc_upflow", "dvc_flow_step", "dvc_bricked_levels", "dvc_corr_backward_mfma", "dvc_corr_backward_gout64",
     "dvc_gru_packed_bytes", "dvc_gru_pack", "dvc_sep_gru_pass",
+    "dvc_conv3_packed_bytes", "dvc_conv3_pack", "dvc_conv3",
+    "dvc_conv7_flow_packed_bytes", "dvc_conv7_flow_pack", "dvc_conv7_flow",
 )
 PROJ_COUT = 96          # DVC_PROJ_COUT (convc1 output channels, update.py:222)
 PROJ_MAX_RADIUS = 4     # DVC_PROJ_MAX_RADIUS
 GRU_HIDDEN = 96         # DVC_GRU_HIDDEN (SepConvGRU3D hidden channels the kernel covers, update.py:283-297)
 GRU_MAX_INPUT = 160     # DVC_GRU_MAX_INPUT
 GRU_SEG = 8             # DVC_GRU_SEG: output positions along the conv axis per workgroup of k_sep_gru_pass
+CONV3_TH, CONV3_TW, CONV3_TD = 4, 4, 16     # DVC_CONV3_TH / TW / TD: output box of one k_conv3_mfma workgroup
+CONV3_MAX_CIN = 128     # DVC_CONV3_MAX_CIN
+CONV3_MAX_COUT = 128    # DVC_CONV3_MAX_COUT
+CONV7_TH, CONV7_TW, CONV7_TD = 4, 4, 16     # DVC_CONV7_TH / TW / TD: output box of one k_conv7_flow workgroup
+CONV7_COUT = 64         # DVC_CONV7_COUT (encoder.convf1, update.py:225)
 
 
 class Layout(ctypes.Structure):
@@ -108,6 +115,12 @@ def lib() -> ctypes.CDLL:
         "dvc_gru_packed_bytes": (sz, [i32, i32, i32]),
         "dvc_gru_pack": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
         "dvc_sep_gru_pass": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "dvc_conv3_packed_bytes": (sz, [i32, i32, i32]),
+        "dvc_conv3_pack": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+        "dvc_conv3": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "dvc_conv7_flow_packed_bytes": (sz, [i32]),
+        "dvc_conv7_flow_pack": (i32, [vp, vp, vp, i32, vp]),
+        "dvc_conv7_flow": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
         "dvc_set_tuning": (i32, [ctypes.c_char_p, i32]),
         "dvc_last_error": (ctypes.c_char_p, []),
         "dvc_version": (ctypes.c_char_p, []),

@@ -21,6 +21,9 @@ the PyTorch dispatcher as named operators with shape functions:
 
     dvccorr::sep_gru(h, x, packed, dtype)        -> h after SepConvGRU3D's three passes  update.py:178-199
                                                  (forward only: no autograd formula is registered)
+    dvccorr::conv3(src0, src1?, packed, dst, dst_offset, cout, relu, dtype)   writes a channel slice of dst:
+                                                 3 x 3 x 3 conv of cat[src0, src1] + bias (+ ReLU)   update.py:226-251
+    dvccorr::conv7_flow(flow, packed, dst, dtype)    dst = relu(convf1(flow))                         update.py:225, 247
 
 Every op runs the HIP kernels of libdvccorr.so through ops.py (no CPU
 fallback); the fake (meta) implementations only compute output shapes, so the
@@ -211,4 +214,26 @@ def _(h, x, packed, dtype):
     return h.new_empty(h.shape, dtype=_F32)
 
 
-__all__ = ["sep_gru", "build", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "lookup_ad", "lookup_convc1_ad"]
+# the update block's plain convolutions: they write a preallocated destination (a channel slice of it for conv3)
+@torch.library.custom_op("dvccorr::conv3", mutates_args=("dst",))
+def conv3(src0: Tensor, src1: Optional[Tensor], packed: Tensor, dst: Tensor, dst_offset: int, cout: int, relu: bool,
+          dtype: int) -> None:
+    ops.conv3(src0, src1, packed, dst, dst_offset, cout, relu, dtype)
+
+
+@conv3.register_fake
+def _(src0, src1, packed, dst, dst_offset, cout, relu, dtype):
+    return None
+
+
+@torch.library.custom_op("dvccorr::conv7_flow", mutates_args=("dst",))
+def conv7_flow(flow: Tensor, packed: Tensor, dst: Tensor, dtype: int) -> None:
+    ops.conv7_flow(flow, packed, dst, dtype)
+
+
+@conv7_flow.register_fake
+def _(flow, packed, dst, dtype):
+    return None
+
+
+__all__ = ["sep_gru", "conv3", "conv7_flow", "build", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "lookup_ad", "lookup_convc1_ad"]

@@ -17,6 +17,9 @@ straight to libdvccorr.so (no CPU fallback).  Shapes follow include/dvccorr.h:
     flow_step(coords1, delta (B, 3, h, w, d), (H,W,D)) -> coords1 + delta, upflow(coords1 + delta - coords0)
     gru_pack(18 SepConvGRU3D tensors, dtype)           -> packed weights of the three axis passes
     sep_gru(h (B, 96, H, W, D), x (B, Ci, H, W, D), packed, dtype) -> h after the h, w and d passes  f32
+    conv3_pack(weight (Co, Ci, 3, 3, 3), bias, dtype)  -> packed weights of one 3 x 3 x 3 convolution
+    conv3(src0, src1 | None, packed, dst, offset, Co, relu, dtype) -> dst[:, offset:offset + Co] written  f32
+    conv7_flow_pack(weight (64, 3, 7, 7, 7), bias, dtype) / conv7_flow(flow, packed, dst, dtype)   encoder.convf1
 """
 from __future__ import annotations
 
@@ -452,3 +455,91 @@ def sep_gru(h: torch.Tensor, x: torch.Tensor, packed: torch.Tensor, dtype: int) 
     sep_gru_pass(a, x, packed[1], b, 1, dtype)
     sep_gru_pass(b, x, packed[2], a, 2, dtype)
     return a
+
+
+def _nbytes(t: torch.Tensor) -> int:
+    return t.numel() * t.element_size()
+
+
+def _conv_operand(t: torch.Tensor, what: str) -> None:
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous float32, got {t.dtype} with strides {tuple(t.stride())}")
+
+
+@_on_device
+def conv3_pack(weight: torch.Tensor, bias: torch.Tensor, dtype: int) -> torch.Tensor:
+    """A (cout, cin, 3, 3, 3) weight and its (cout) bias -> the packed MFMA operands and biases of dvc_conv3
+    (dvc_conv3_pack; dvc_conv3_packed_bytes)."""
+    _need_cuda(weight, bias)
+    if weight.ndim != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError(f"conv3_pack: weight {tuple(weight.shape)} bias {tuple(bias.shape)} are not a 3 x 3 x 3 "
+                         "convolution's")
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    nbytes = lib().dvc_conv3_packed_bytes(cin, cout, dtype)
+    if nbytes == 0:
+        raise NotImplementedError(f"conv3_pack: cin={cin} cout={cout} is outside the kernel's shapes "
+                                  f"(cin 1..{_lib.CONV3_MAX_CIN}, cout 1..{_lib.CONV3_MAX_COUT})")
+    w, b = _f32c(weight.detach()), _f32c(bias.detach())
+    out = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
+    check(lib().dvc_conv3_pack(_ptr(w), _ptr(b), _ptr(out), cin, cout, dtype, _stream(w)), "conv3_pack")
+    return out
+
+
+@_on_device
+def conv3(src0: torch.Tensor, src1, packed: torch.Tensor, dst: torch.Tensor, dst_offset: int, cout: int, relu: bool,
+          dtype: int) -> torch.Tensor:
+    """dst[:, dst_offset:dst_offset + cout] = conv3x3x3(cat[src0, src1]) + bias (+ ReLU) (dvc_conv3); src1 may be
+    None.  All tensors contiguous float32 (B, C, H, W, D); dst is written in place and returned."""
+    ts = [src0, dst] + ([] if src1 is None else [src1])
+    _need_cuda(packed, *ts)
+    for t in ts:
+        _conv_operand(t, "conv3: sources and dst")
+        if t.ndim != 5 or t.shape[0] != src0.shape[0] or t.shape[2:] != src0.shape[2:]:
+            raise ValueError(f"conv3: sources and dst must be (B, C, H, W, D) of one batch and volume; got "
+                             f"{[tuple(v.shape) for v in ts]}")
+    B, c0, H, W, D = src0.shape
+    c1 = 0 if src1 is None else int(src1.shape[1])
+    need = lib().dvc_conv3_packed_bytes(c0 + c1, cout, dtype)
+    if need == 0 or _nbytes(packed) != need:
+        raise ValueError(f"conv3: packed weights of {_nbytes(packed)} bytes; cin {c0 + c1}, cout {cout} and this "
+                         f"precision take {need} (conv3_pack with the same dtype)")
+    check(lib().dvc_conv3(_ptr(src0), c0, None if src1 is None else _ptr(src1), c1, _ptr(packed), _ptr(dst),
+                          int(dst.shape[1]), int(dst_offset), int(cout), int(bool(relu)), B, H, W, D, dtype,
+                          _stream(src0)), "conv3")
+    return dst
+
+
+@_on_device
+def conv7_flow_pack(weight: torch.Tensor, bias: torch.Tensor, dtype: int) -> torch.Tensor:
+    """encoder.convf1's (64, 3, 7, 7, 7) weight and (64) bias -> the packed operands of dvc_conv7_flow."""
+    _need_cuda(weight, bias)
+    if tuple(weight.shape) != (_lib.CONV7_COUT, 3, 7, 7, 7) or tuple(bias.shape) != (_lib.CONV7_COUT,):
+        raise NotImplementedError(f"conv7_flow_pack: weight {tuple(weight.shape)} bias {tuple(bias.shape)}; the "
+                                  f"kernel covers ({_lib.CONV7_COUT}, 3, 7, 7, 7)")
+    nbytes = lib().dvc_conv7_flow_packed_bytes(dtype)
+    if nbytes == 0:
+        raise ValueError(f"conv7_flow_pack: bad dtype {dtype}")
+    w, b = _f32c(weight.detach()), _f32c(bias.detach())
+    out = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
+    check(lib().dvc_conv7_flow_pack(_ptr(w), _ptr(b), _ptr(out), dtype, _stream(w)), "conv7_flow_pack")
+    return out
+
+
+@_on_device
+def conv7_flow(flow: torch.Tensor, packed: torch.Tensor, dst: torch.Tensor, dtype: int) -> torch.Tensor:
+    """dst = relu(convf1(flow)): flow (B, 3, H, W, D), dst (B, 64, H, W, D), contiguous float32 (dvc_conv7_flow);
+    dst is written in place and returned."""
+    _need_cuda(flow, packed, dst)
+    _conv_operand(flow, "conv7_flow: flow")
+    _conv_operand(dst, "conv7_flow: dst")
+    if flow.ndim != 5 or dst.ndim != 5 or flow.shape[1] != 3 or dst.shape[1] != _lib.CONV7_COUT \
+            or dst.shape[0] != flow.shape[0] or dst.shape[2:] != flow.shape[2:]:
+        raise ValueError(f"conv7_flow: flow must be (B, 3, H, W, D) and dst (B, {_lib.CONV7_COUT}, H, W, D); got "
+                         f"{tuple(flow.shape)} and {tuple(dst.shape)}")
+    need = lib().dvc_conv7_flow_packed_bytes(dtype)
+    if need == 0 or _nbytes(packed) != need:
+        raise ValueError(f"conv7_flow: packed weights of {_nbytes(packed)} bytes; this precision takes {need} "
+                         "(conv7_flow_pack with the same dtype)")
+    B, _, H, W, D = flow.shape
+    check(lib().dvc_conv7_flow(_ptr(flow), _ptr(packed), _ptr(dst), B, H, W, D, dtype, _stream(flow)), "conv7_flow")
+    return dst
