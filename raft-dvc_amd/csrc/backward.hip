@@ -42,9 +42,6 @@
 
 namespace dvc {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // LDS-DMA (global_load_lds_dword / _dwordx4): each lane's 4 / 16 bytes from its own global address land at
 // LDS byte lds + 4 / 16 * lane (lds wave-uniform).  Issued from asm so hipcc leaves them out of its s_waitcnt
 // bookkeeping (it would otherwise drain them with vmcnt(0) before every LDS read): the kernel counts them

@@ -22,9 +22,6 @@
 
 namespace dvc {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 // ----------------------------------------------------------------------------- bf16
 // tile: 128 queries x 128 columns, 256 threads (4 waves as 2 (cols) x 2 (queries)),
 // each wave 64 x 64 = 2 x 2 accumulators of v_mfma_f32_32x32x16_bf16.

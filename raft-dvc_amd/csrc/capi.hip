@@ -134,9 +134,24 @@ static int fail(int code, const char *fmt, ...) {
     return code;
 }
 
-static int check_launch(const char *what) {
-    hipError_t e = hipGetLastError();
+static int launched(const char *what, hipError_t e) {
     if (e != hipSuccess) return fail(DVC_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
+    return DVC_OK;
+}
+
+static int check_launch(const char *what) { return launched(what, hipGetLastError()); }
+
+static int dtype_ok(const char *what, int dtype) {
+    if (dtype != DVC_BF16 && dtype != DVC_F32 && dtype != DVC_F16)
+        return fail(DVC_ERR_INVALID, "%s: bad dtype %d", what, dtype);
+    return DVC_OK;
+}
+
+// a (B, *, H, W, D) tensor's sizes are positive and its voxels can be counted in 32 bits
+static int volume_check(const char *what, int B, int H, int W, int D, const char *indices = "indices") {
+    if (B < 1 || H < 1 || W < 1 || D < 1) return fail(DVC_ERR_INVALID, "%s: B=%d volume (%d,%d,%d)", what, B, H, W, D);
+    const long long vox = (long long)B * H * W * D;
+    if (vox >= (1LL << 31)) return fail(DVC_ERR_UNSUPPORTED, "%s: %lld voxels exceed 32-bit %s", what, vox, indices);
     return DVC_OK;
 }
 
@@ -1170,8 +1185,7 @@ int dvc_flow_step(const float *coords1, const float *delta_flow, float *coords1_
 
 // SepConvGRU3D forward (gru.hip): the shapes k_sep_gru_pass covers
 static int gru_shape_check(const char *what, int hidden, int input, int dtype) {
-    if (dtype != DVC_BF16 && dtype != DVC_F32 && dtype != DVC_F16)
-        return fail(DVC_ERR_INVALID, "%s: bad dtype %d", what, dtype);
+    if (int rc = dtype_ok(what, dtype)) return rc;
     if (hidden != DVC_GRU_HIDDEN || input < 1 || input > DVC_GRU_MAX_INPUT)
         return fail(DVC_ERR_UNSUPPORTED, "%s: hidden=%d input=%d (the kernel covers hidden %d, input 1..%d)", what,
                     hidden, input, DVC_GRU_HIDDEN, DVC_GRU_MAX_INPUT);
@@ -1187,32 +1201,26 @@ int dvc_gru_pack(const float *wz, const float *wr, const float *wq, const float 
                  const float *bq, void *packed, int hidden, int input, int dtype, void *stream) {
     if (!wz || !wr || !wq || !bz || !br || !bq || !packed) return fail(DVC_ERR_INVALID, "gru_pack: null pointer");
     if (int rc = gru_shape_check("gru_pack", hidden, input, dtype)) return rc;
-    hipError_t e = launch_gru_pack(wz, wr, wq, bz, br, bq, packed, input, dtype, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DVC_ERR_LAUNCH, "gru_pack: %s", hipGetErrorString(e));
-    return DVC_OK;
+    return launched("gru_pack", launch_gru_pack(wz, wr, wq, bz, br, bq, packed, input, dtype, (hipStream_t)stream));
 }
 
 int dvc_sep_gru_pass(const float *h, const float *x, const void *packed, float *h_out, int B, int hidden, int input,
                      int H, int W, int D, int axis, int dtype, void *stream) {
     if (!h || !x || !packed || !h_out) return fail(DVC_ERR_INVALID, "sep_gru_pass: null pointer");
-    if (B < 1 || H < 1 || W < 1 || D < 1)
-        return fail(DVC_ERR_INVALID, "sep_gru_pass: B=%d volume (%d,%d,%d)", B, H, W, D);
+    if (int rc = volume_check("sep_gru_pass", B, H, W, D, "line indices")) return rc;
     if (axis < 0 || axis > 2) return fail(DVC_ERR_INVALID, "sep_gru_pass: axis %d is not 0 (h), 1 (w) or 2 (d)", axis);
     if (int rc = gru_shape_check("sep_gru_pass", hidden, input, dtype)) return rc;
     const long long vox = (long long)B * H * W * D;
-    if (vox >= (1LL << 31)) return fail(DVC_ERR_UNSUPPORTED, "sep_gru_pass: %lld voxels exceed 32-bit line indices", vox);
     const size_t hb = (size_t)vox * hidden * 4, xb = (size_t)vox * input * 4;
     if (overlaps(h_out, hb, h, hb) || overlaps(h_out, hb, x, xb))
         return fail(DVC_ERR_INVALID, "sep_gru_pass: h_out must not overlap h or x (a pass reads its neighbours)");
-    hipError_t e = launch_sep_gru_pass(h, x, packed, h_out, B, input, H, W, D, axis, dtype, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DVC_ERR_LAUNCH, "sep_gru_pass: %s", hipGetErrorString(e));
-    return DVC_OK;
+    return launched("sep_gru_pass",
+                    launch_sep_gru_pass(h, x, packed, h_out, B, input, H, W, D, axis, dtype, (hipStream_t)stream));
 }
 
 // the update block's plain convolutions (conv3.hip): the shapes k_conv3_mfma covers
 static int conv3_shape_check(const char *what, int cin, int cout, int dtype) {
-    if (dtype != DVC_BF16 && dtype != DVC_F32 && dtype != DVC_F16)
-        return fail(DVC_ERR_INVALID, "%s: bad dtype %d", what, dtype);
+    if (int rc = dtype_ok(what, dtype)) return rc;
     if (cin < 1 || cout < 1) return fail(DVC_ERR_INVALID, "%s: cin=%d cout=%d", what, cin, cout);
     if (cin > DVC_CONV3_MAX_CIN || cout > DVC_CONV3_MAX_COUT)
         return fail(DVC_ERR_UNSUPPORTED, "%s: cin=%d cout=%d (the kernel covers cin 1..%d, cout 1..%d)", what, cin,
@@ -1228,15 +1236,13 @@ size_t dvc_conv3_packed_bytes(int cin, int cout, int dtype) {
 int dvc_conv3_pack(const float *w, const float *bias, void *packed, int cin, int cout, int dtype, void *stream) {
     if (!w || !bias || !packed) return fail(DVC_ERR_INVALID, "conv3_pack: null pointer");
     if (int rc = conv3_shape_check("conv3_pack", cin, cout, dtype)) return rc;
-    hipError_t e = launch_conv3_pack(w, bias, packed, cin, cout, dtype, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DVC_ERR_LAUNCH, "conv3_pack: %s", hipGetErrorString(e));
-    return DVC_OK;
+    return launched("conv3_pack", launch_conv3_pack(w, bias, packed, cin, cout, dtype, (hipStream_t)stream));
 }
 
 int dvc_conv3(const float *src0, int c0, const float *src1, int c1, const void *packed, float *dst, int dst_channels,
               int dst_offset, int cout, int relu, int B, int H, int W, int D, int dtype, void *stream) {
     if (!src0 || !packed || !dst) return fail(DVC_ERR_INVALID, "conv3: null pointer");
-    if (B < 1 || H < 1 || W < 1 || D < 1) return fail(DVC_ERR_INVALID, "conv3: B=%d volume (%d,%d,%d)", B, H, W, D);
+    if (int rc = volume_check("conv3", B, H, W, D)) return rc;
     if (!src1) c1 = 0;
     if (c0 < 1 || c1 < 0 || (src1 && c1 < 1)) return fail(DVC_ERR_INVALID, "conv3: c0=%d c1=%d", c0, c1);
     if (c0 > DVC_CONV3_MAX_CIN || c1 > DVC_CONV3_MAX_CIN)
@@ -1247,14 +1253,11 @@ int dvc_conv3(const float *src0, int c0, const float *src1, int c1, const void *
         return fail(DVC_ERR_INVALID, "conv3: channels [%d, %d + %d) are not inside dst's %d", dst_offset, dst_offset,
                     cout, dst_channels);
     const long long vox = (long long)B * H * W * D;
-    if (vox >= (1LL << 31)) return fail(DVC_ERR_UNSUPPORTED, "conv3: %lld voxels exceed 32-bit indices", vox);
     const size_t db = (size_t)vox * dst_channels * 4;
     if (overlaps(dst, db, src0, (size_t)vox * c0 * 4) || (src1 && overlaps(dst, db, src1, (size_t)vox * c1 * 4)))
         return fail(DVC_ERR_INVALID, "conv3: dst must not overlap a source (a voxel reads its neighbours)");
-    hipError_t e = launch_conv3(src0, c0, src1, c1, packed, dst, dst_channels, dst_offset, cout, relu != 0, B, H, W, D,
-                                dtype, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DVC_ERR_LAUNCH, "conv3: %s", hipGetErrorString(e));
-    return DVC_OK;
+    return launched("conv3", launch_conv3(src0, c0, src1, c1, packed, dst, dst_channels, dst_offset, cout, relu != 0, B,
+                                          H, W, D, dtype, (hipStream_t)stream));
 }
 
 size_t dvc_conv7_flow_packed_bytes(int dtype) {
@@ -1264,27 +1267,19 @@ size_t dvc_conv7_flow_packed_bytes(int dtype) {
 
 int dvc_conv7_flow_pack(const float *w, const float *bias, void *packed, int dtype, void *stream) {
     if (!w || !bias || !packed) return fail(DVC_ERR_INVALID, "conv7_flow_pack: null pointer");
-    if (dtype != DVC_BF16 && dtype != DVC_F32 && dtype != DVC_F16)
-        return fail(DVC_ERR_INVALID, "conv7_flow_pack: bad dtype %d", dtype);
-    hipError_t e = launch_conv7_pack(w, bias, packed, dtype, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DVC_ERR_LAUNCH, "conv7_flow_pack: %s", hipGetErrorString(e));
-    return DVC_OK;
+    if (int rc = dtype_ok("conv7_flow_pack", dtype)) return rc;
+    return launched("conv7_flow_pack", launch_conv7_pack(w, bias, packed, dtype, (hipStream_t)stream));
 }
 
 int dvc_conv7_flow(const float *flow, const void *packed, float *dst, int B, int H, int W, int D, int dtype,
                    void *stream) {
     if (!flow || !packed || !dst) return fail(DVC_ERR_INVALID, "conv7_flow: null pointer");
-    if (B < 1 || H < 1 || W < 1 || D < 1)
-        return fail(DVC_ERR_INVALID, "conv7_flow: B=%d volume (%d,%d,%d)", B, H, W, D);
-    if (dtype != DVC_BF16 && dtype != DVC_F32 && dtype != DVC_F16)
-        return fail(DVC_ERR_INVALID, "conv7_flow: bad dtype %d", dtype);
+    if (int rc = volume_check("conv7_flow", B, H, W, D)) return rc;
+    if (int rc = dtype_ok("conv7_flow", dtype)) return rc;
     const long long vox = (long long)B * H * W * D;
-    if (vox >= (1LL << 31)) return fail(DVC_ERR_UNSUPPORTED, "conv7_flow: %lld voxels exceed 32-bit indices", vox);
     if (overlaps(dst, (size_t)vox * DVC_CONV7_COUT * 4, flow, (size_t)vox * 3 * 4))
         return fail(DVC_ERR_INVALID, "conv7_flow: dst must not overlap flow (a voxel reads its neighbours)");
-    hipError_t e = launch_conv7_flow(flow, packed, dst, B, H, W, D, dtype, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DVC_ERR_LAUNCH, "conv7_flow: %s", hipGetErrorString(e));
-    return DVC_OK;
+    return launched("conv7_flow", launch_conv7_flow(flow, packed, dst, B, H, W, D, dtype, (hipStream_t)stream));
 }
 
 }  // extern "C"
@@ -1305,8 +1300,7 @@ int dvc_corr_lookup_fused_proj(const void *packed_q, const void *packed_t, const
     if (B < 1 || Nq < 1) return fail(DVC_ERR_INVALID, "lookup_fused_proj: B=%d Nq=%lld", B, (long long)Nq);
     if (convention != DVC_FIXED && convention != DVC_LEGACY)
         return fail(DVC_ERR_INVALID, "lookup_fused_proj: bad convention %d", convention);
-    if (dtype != DVC_BF16 && dtype != DVC_F32 && dtype != DVC_F16)
-        return fail(DVC_ERR_INVALID, "lookup_fused_proj: bad dtype %d", dtype);
+    if ((rc = dtype_ok("lookup_fused_proj", dtype))) return rc;
     return fused_lookup_proj(packed_q, packed_t, coords, packed_w, bias, out, workspace, B, Nq, C, lay, radius,
                              convention, dtype, g_fused_ablate, (hipStream_t)stream, g_err, sizeof(g_err));
 }

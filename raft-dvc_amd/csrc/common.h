@@ -22,13 +22,18 @@
 #define DVC_PROJ_XLP 0
 #endif
 
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short bf16_t;   // storage type of one bf16 value
 typedef _Float16 f16_t;          // storage type of one fp16 value (the AMP pyramid, trainer.py:249-252)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace dvc {
 

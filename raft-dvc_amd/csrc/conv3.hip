@@ -27,20 +27,14 @@
 // column groups bh = w with all four output tiles.
 //
 // No atomics, no allocation or synchronisation on the host.
-#include "common.h"
-
-#include <type_traits>
+#include "mfma_conv.h"
 
 namespace dvc {
-
-typedef float cf4 __attribute__((ext_vector_type(4)));
-typedef _Float16 c3_f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int C3_TH = DVC_CONV3_TH, C3_TW = DVC_CONV3_TW, C3_TD = DVC_CONV3_TD;
 constexpr int C3_HW = C3_TW + 2, C3_HD = C3_TD + 2;
 constexpr int C3_ROWS = (C3_TH + 2) * C3_HW * C3_HD;   // 648 halo voxels
-constexpr int C3_ROWB = 80;
-constexpr int C3_PIECE = C3_ROWS * C3_ROWB;
+constexpr int C3_PIECE = C3_ROWS * kRowBytes;
 constexpr int C3_STAGE = (C3_ROWS + 255) / 256;        // halo rows per thread
 static_assert(C3_TH == 4 && C3_TW == 4 && C3_TD == 16, "sixteen column groups of 16 voxels, four per wave");
 
@@ -52,33 +46,6 @@ struct Conv3Args {
     int B, C0, C1, H, W, D, dstC, dstOff, cout, relu, nch, nth, ntw, ntd;
 };
 
-template <typename T> __device__ __forceinline__ cf4 c3_mma(u32x4 a, u32x4 b, cf4 c);
-template <> __device__ __forceinline__ cf4 c3_mma<bf16_t>(u32x4 a, u32x4 b, cf4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                   0, 0);
-}
-template <> __device__ __forceinline__ cf4 c3_mma<f16_t>(u32x4 a, u32x4 b, cf4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(c3_f16x8, a), __builtin_bit_cast(c3_f16x8, b), c,
-                                                  0, 0, 0);
-}
-
-// one accumulator step: NP = 1 one product, NP = 2 the three products of the hi + lo split
-template <typename T, int NP>
-__device__ __forceinline__ cf4 c3_step(const u32x4 (&a)[NP], const u32x4 (&b)[NP], cf4 d) {
-    if constexpr (NP == 2) {
-        d = c3_mma<T>(a[1], b[0], d);
-        d = c3_mma<T>(a[0], b[1], d);
-    }
-    return c3_mma<T>(a[0], b[0], d);
-}
-
-// two fp32 values -> one dword of 16-bit hi pieces and (NP = 2) one of lo pieces
-template <typename T, int NP> __device__ __forceinline__ void c3_split2(float a, float b, unsigned &hi, unsigned &lo) {
-    hi = pack2_16<T>(a, b);
-    lo = 0u;
-    if constexpr (NP == 2) lo = pack2_16<T>(a - bits16_to_f32<T>(hi), b - bits16_to_f32<T>(hi >> 16));
-}
-
 template <typename T, int NP, int FULL, int SHARED>
 __global__ __launch_bounds__(256, 1) void k_conv3_mfma(Conv3Args A) {
     constexpr int NT = 4 * FULL + SHARED;   // packed tiles
@@ -86,13 +53,8 @@ __global__ __launch_bounds__(256, 1) void k_conv3_mfma(Conv3Args A) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[NP * C3_PIECE];
     const int tid = threadIdx.x, lane = tid & 63, m16 = lane & 15, h4 = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    unsigned bid = blockIdx.x;
-    const int d0 = (int)(bid % (unsigned)A.ntd) * C3_TD;
-    bid /= (unsigned)A.ntd;
-    const int w0 = (int)(bid % (unsigned)A.ntw) * C3_TW;
-    bid /= (unsigned)A.ntw;
-    const int h0 = (int)(bid % (unsigned)A.nth) * C3_TH;
-    const int b = (int)(bid / (unsigned)A.nth);
+    int b, h0, w0, d0;
+    box_of_block(blockIdx.x, A.nth, A.ntw, A.ntd, C3_TH, C3_TW, C3_TD, b, h0, w0, d0);
     const long long HWD = A.HWD;
     const int cin = A.C0 + A.C1;
     const float *s0 = A.s0 + (long long)b * A.C0 * HWD;
@@ -124,19 +86,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3_mfma(Conv3Args A) {
 #pragma unroll
         for (int i = 0; i < C3_STAGE; ++i) {
             const int r = tid + 256 * i;
-            if (r < C3_ROWS) {
-                unsigned char *srow = smem + r * C3_ROWB;
-#pragma unroll
-                for (int o = 0; o < 4; ++o) {
-                    unsigned hi[4], lo[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        c3_split2<T, NP>(st[i][8 * o + 2 * j], st[i][8 * o + 2 * j + 1], hi[j], lo[j]);
-                    *reinterpret_cast<u32x4 *>(srow + o * 16) = u32x4{hi[0], hi[1], hi[2], hi[3]};
-                    if constexpr (NP == 2)
-                        *reinterpret_cast<u32x4 *>(srow + C3_PIECE + o * 16) = u32x4{lo[0], lo[1], lo[2], lo[3]};
-                }
-            }
+            if (r < C3_ROWS) stage_row<T, NP>(st[i], smem + r * kRowBytes, C3_PIECE);
         }
     };
 
@@ -145,28 +95,28 @@ __global__ __launch_bounds__(256, 1) void k_conv3_mfma(Conv3Args A) {
     const int nunits = A.nch * 27;
     u32x4 wc[NW][NP], wn[NW][NP];
     auto loadw = [&](int u, u32x4 (&wf)[NW][NP]) __attribute__((always_inline)) {
-        const unsigned char *p = wbase + (long long)(u < nunits ? u : nunits - 1) * NT * NP * 1024;
+        const unsigned char *p = wbase + (long long)(u < nunits ? u : nunits - 1) * NT * NP * kFragBytes;
 #pragma unroll
         for (int f = 0; f < FULL; ++f)
 #pragma unroll
             for (int pc = 0; pc < NP; ++pc)
-                wf[f][pc] = *reinterpret_cast<const u32x4 *>(p + ((wave + 4 * f) * NP + pc) * 1024);
+                wf[f][pc] = *reinterpret_cast<const u32x4 *>(p + ((wave + 4 * f) * NP + pc) * kFragBytes);
 #pragma unroll
         for (int s = 0; s < SHARED; ++s)
 #pragma unroll
             for (int pc = 0; pc < NP; ++pc)
-                wf[FULL + s][pc] = *reinterpret_cast<const u32x4 *>(p + ((4 * FULL + s) * NP + pc) * 1024);
+                wf[FULL + s][pc] = *reinterpret_cast<const u32x4 *>(p + ((4 * FULL + s) * NP + pc) * kFragBytes);
     };
 
-    cf4 accf[FULL > 0 ? FULL : 1][16], accs[SHARED > 0 ? SHARED : 1][4];
+    f32x4 accf[FULL > 0 ? FULL : 1][16], accs[SHARED > 0 ? SHARED : 1][4];
 #pragma unroll
     for (int f = 0; f < (FULL > 0 ? FULL : 1); ++f)
 #pragma unroll
-        for (int g = 0; g < 16; ++g) accf[f][g] = cf4{0.f, 0.f, 0.f, 0.f};
+        for (int g = 0; g < 16; ++g) accf[f][g] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < (SHARED > 0 ? SHARED : 1); ++s)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) accs[s][g] = cf4{0.f, 0.f, 0.f, 0.f};
+        for (int g = 0; g < 4; ++g) accs[s][g] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     int u = 0;
     loadw(0, wc);
@@ -180,7 +130,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3_mfma(Conv3Args A) {
 #pragma unroll 1
         for (int hw = 0; hw < 9; ++hw) {
             const int dh = hw / 3, dw = hw - 3 * dh;
-            const unsigned char *lb = smem + ((dh * C3_HW + dw) * C3_HD + m16) * C3_ROWB + h4 * 16;
+            const unsigned char *lb = smem + ((dh * C3_HW + dw) * C3_HD + m16) * kRowBytes + h4 * 16;
 #pragma unroll
             for (int dd = 0; dd < 3; ++dd) {
                 ++u;
@@ -192,21 +142,21 @@ __global__ __launch_bounds__(256, 1) void k_conv3_mfma(Conv3Args A) {
 #pragma unroll
                         for (int pc = 0; pc < NP; ++pc)
                             bf[pc] = *reinterpret_cast<const u32x4 *>(
-                                lb + pc * C3_PIECE + (((g >> 2) * C3_HW + (g & 3)) * C3_HD + dd) * C3_ROWB);
+                                lb + pc * C3_PIECE + (((g >> 2) * C3_HW + (g & 3)) * C3_HD + dd) * kRowBytes);
 #pragma unroll
-                        for (int f = 0; f < FULL; ++f) accf[f][g] = c3_step<T, NP>(wc[f], bf, accf[f][g]);
+                        for (int f = 0; f < FULL; ++f) accf[f][g] = mma_step<T, NP>(wc[f], bf, accf[f][g]);
                     }
                 }
                 if constexpr (SHARED > 0) {
-                    const unsigned char *ls = lb + wave * (C3_HW * C3_HD * C3_ROWB);
+                    const unsigned char *ls = lb + wave * (C3_HW * C3_HD * kRowBytes);
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         u32x4 bf[NP];
 #pragma unroll
                         for (int pc = 0; pc < NP; ++pc)
-                            bf[pc] = *reinterpret_cast<const u32x4 *>(ls + pc * C3_PIECE + (g * C3_HD + dd) * C3_ROWB);
+                            bf[pc] = *reinterpret_cast<const u32x4 *>(ls + pc * C3_PIECE + (g * C3_HD + dd) * kRowBytes);
 #pragma unroll
-                        for (int s = 0; s < SHARED; ++s) accs[s][g] = c3_step<T, NP>(wc[FULL + s], bf, accs[s][g]);
+                        for (int s = 0; s < SHARED; ++s) accs[s][g] = mma_step<T, NP>(wc[FULL + s], bf, accs[s][g]);
                     }
                 }
 #pragma unroll
@@ -218,10 +168,10 @@ __global__ __launch_bounds__(256, 1) void k_conv3_mfma(Conv3Args A) {
     }
 
     // bias, ReLU, store: lane (m16, h4) holds voxel d0 + m16 of its column group, channels 16 tile + 4 h4 + k
-    const float *bias = reinterpret_cast<const float *>(A.w + (long long)nunits * NT * NP * 1024);
+    const float *bias = reinterpret_cast<const float *>(A.w + (long long)nunits * NT * NP * kFragBytes);
     float *dst = A.dst + ((long long)b * A.dstC + A.dstOff) * HWD;
     const int d = d0 + m16;
-    auto store = [&](int tile, int bh, int bw, cf4 v) __attribute__((always_inline)) {
+    auto store = [&](int tile, int bh, int bw, f32x4 v) __attribute__((always_inline)) {
         const int h = h0 + bh, w = w0 + bw;
         if (h >= A.H || w >= A.W || d >= A.D) return;
         const long long vox = ((long long)h * A.W + w) * A.D + d;
@@ -258,17 +208,14 @@ __global__ __launch_bounds__(256) void k_conv3_pack(const float *__restrict__ w,
     const int nfr = nch * 27 * nt;
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= nfr * 512) return;
-    const int j = e & 7, l = (e >> 3) & 63, fr = e >> 9;
+    int fr, l, j;
+    frag_elem(e, fr, l, j);
     const int tile = fr % nt, ct = fr / nt, c = ct / 27, t = ct - 27 * c;
     const int o = 16 * tile + (l & 15), kp = 32 * c + 8 * (l >> 4) + j;
     const float v = o < cout && kp < cin ? w[((long long)o * cin + kp) * 27 + t] : 0.0f;
-    T *dst = reinterpret_cast<T *>(out + (long long)fr * NP * 1024) + l * 8 + j;
-    T hi;
-    StoreT<T>::store(&hi, v);
-    dst[0] = hi;
-    if constexpr (NP == 2) StoreT<T>::store(dst + 512, v - StoreT<T>::load(&hi));
+    pack_store<T, NP>(out, fr, l, j, v);
     if (e < 16 * nt) {
-        float *bo = reinterpret_cast<float *>(out + (long long)nfr * NP * 1024);
+        float *bo = reinterpret_cast<float *>(out + (long long)nfr * NP * kFragBytes);
         bo[e] = e < cout ? bias[e] : 0.0f;
     }
 }
@@ -281,7 +228,7 @@ static int conv3_tiles(int cout) {
 
 size_t conv3_packed_bytes(int cin, int cout, int dtype) {
     const int nt = conv3_tiles(cout), nch = (cin + 31) / 32;
-    return (size_t)nch * 27 * nt * (dtype == DVC_F32 ? 2 : 1) * 1024 + (size_t)16 * nt * sizeof(float);
+    return (size_t)nch * 27 * nt * pieces_of(dtype) * kFragBytes + (size_t)16 * nt * sizeof(float);
 }
 
 hipError_t launch_conv3_pack(const float *w, const float *bias, void *packed, int cin, int cout, int dtype,
@@ -289,17 +236,17 @@ hipError_t launch_conv3_pack(const float *w, const float *bias, void *packed, in
     const int nt = conv3_tiles(cout), nch = (cin + 31) / 32;
     const unsigned blocks = (unsigned)(nch * 27 * nt * 512 / 256);
     unsigned char *out = static_cast<unsigned char *>(packed);
-    if (dtype == DVC_F32) k_conv3_pack<bf16_t, 2><<<blocks, 256, 0, s>>>(w, bias, out, cin, cout, nch, nt);
-    else if (dtype == DVC_BF16) k_conv3_pack<bf16_t, 1><<<blocks, 256, 0, s>>>(w, bias, out, cin, cout, nch, nt);
-    else k_conv3_pack<f16_t, 1><<<blocks, 256, 0, s>>>(w, bias, out, cin, cout, nch, nt);
+    with_precision(dtype, [&](auto t, auto np) {
+        k_conv3_pack<decltype(t), decltype(np)::value><<<blocks, 256, 0, s>>>(w, bias, out, cin, cout, nch, nt);
+    });
     return hipGetLastError();
 }
 
 template <int FULL, int SHARED>
 static void conv3_launch(const Conv3Args &A, unsigned grid, int dtype, hipStream_t s) {
-    if (dtype == DVC_F32) k_conv3_mfma<bf16_t, 2, FULL, SHARED><<<grid, 256, 0, s>>>(A);
-    else if (dtype == DVC_BF16) k_conv3_mfma<bf16_t, 1, FULL, SHARED><<<grid, 256, 0, s>>>(A);
-    else k_conv3_mfma<f16_t, 1, FULL, SHARED><<<grid, 256, 0, s>>>(A);
+    with_precision(dtype, [&](auto t, auto np) {
+        k_conv3_mfma<decltype(t), decltype(np)::value, FULL, SHARED><<<grid, 256, 0, s>>>(A);
+    });
 }
 
 // host entry: arguments validated by dvc_conv3 (capi.hip)
@@ -346,13 +293,8 @@ __global__ __launch_bounds__(256, 1) void k_conv7_flow(Conv7Args A) {
     __shared__ float tile[3 * C7_CH];
     const int tid = threadIdx.x, lane = tid & 63, m16 = lane & 15, h4 = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    unsigned bid = blockIdx.x;
-    const int d0 = (int)(bid % (unsigned)A.ntd) * C7_TD;
-    bid /= (unsigned)A.ntd;
-    const int w0 = (int)(bid % (unsigned)A.ntw) * C7_TW;
-    bid /= (unsigned)A.ntw;
-    const int h0 = (int)(bid % (unsigned)A.nth) * C7_TH;
-    const int b = (int)(bid / (unsigned)A.nth);
+    int b, h0, w0, d0;
+    box_of_block(blockIdx.x, A.nth, A.ntw, A.ntd, C7_TH, C7_TW, C7_TD, b, h0, w0, d0);
     const long long HWD = A.HWD;
     const float *src = A.flow + (long long)b * 3 * HWD;
 
@@ -367,26 +309,19 @@ __global__ __launch_bounds__(256, 1) void k_conv7_flow(Conv7Args A) {
 
     const unsigned char *wbase = A.w + lane * 16;
     u32x4 wc[4][NP], wn[4][NP];
-    auto loadw = [&](int u, u32x4 (&wf)[4][NP]) __attribute__((always_inline)) {
-        const unsigned char *p = wbase + (long long)(u < C7_STEPS ? u : C7_STEPS - 1) * 4 * NP * 1024;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int pc = 0; pc < NP; ++pc) wf[t][pc] = *reinterpret_cast<const u32x4 *>(p + (t * NP + pc) * 1024);
-    };
-    cf4 acc[4][4];
+    f32x4 acc[4][4];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) acc[t][g] = cf4{0.f, 0.f, 0.f, 0.f};
+        for (int g = 0; g < 4; ++g) acc[t][g] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // lane group h4 = input channel (the fourth group is zeros), element j = kd
     const float *lb = tile + (h4 < 3 ? h4 : 0) * C7_CH + wave * (C7_HW * C7_HD) + m16;
-    loadw(0, wc);
+    load_frags(wbase, 0, C7_STEPS, 4, wc);
 #pragma unroll 1
     for (int u = 0; u < C7_STEPS; ++u) {
         const int kh = u / 7, kw = u - 7 * kh;
-        loadw(u + 1, wn);
+        load_frags(wbase, u + 1, C7_STEPS, 4, wn);
         const float *lp = lb + (kh * C7_HW + kw) * C7_HD;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -396,12 +331,12 @@ __global__ __launch_bounds__(256, 1) void k_conv7_flow(Conv7Args A) {
             f[7] = 0.0f;
             unsigned hi[4], lo[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) c3_split2<T, NP>(f[2 * j], f[2 * j + 1], hi[j], lo[j]);
+            for (int j = 0; j < 4; ++j) split2<T, NP>(f[2 * j], f[2 * j + 1], hi[j], lo[j]);
             u32x4 bf[NP];
             bf[0] = u32x4{hi[0], hi[1], hi[2], hi[3]};
             if constexpr (NP == 2) bf[1] = u32x4{lo[0], lo[1], lo[2], lo[3]};
 #pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t][g] = c3_step<T, NP>(wc[t], bf, acc[t][g]);
+            for (int t = 0; t < 4; ++t) acc[t][g] = mma_step<T, NP>(wc[t], bf, acc[t][g]);
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t)
@@ -409,7 +344,7 @@ __global__ __launch_bounds__(256, 1) void k_conv7_flow(Conv7Args A) {
             for (int pc = 0; pc < NP; ++pc) wc[t][pc] = wn[t][pc];
     }
 
-    const float *bias = reinterpret_cast<const float *>(A.w + (long long)C7_STEPS * 4 * NP * 1024);
+    const float *bias = reinterpret_cast<const float *>(A.w + (long long)C7_STEPS * 4 * NP * kFragBytes);
     float *dst = A.dst + (long long)b * C7_COUT * HWD;
     const int h = h0 + wave, d = d0 + m16;
 #pragma unroll
@@ -434,28 +369,25 @@ __global__ __launch_bounds__(256) void k_conv7_pack(const float *__restrict__ w,
                                                     unsigned char *__restrict__ out) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= C7_STEPS * 4 * 512) return;
-    const int j = e & 7, l = (e >> 3) & 63, fr = e >> 9;
+    int fr, l, j;
+    frag_elem(e, fr, l, j);
     const int tile = fr & 3, u = fr >> 2, kh = u / 7, kw = u - 7 * kh;
     const int o = 16 * tile + (l & 15), ci = l >> 4;
     const float v = ci < 3 && j < 7 ? w[((long long)(o * 3 + ci) * 7 + kh) * 49 + kw * 7 + j] : 0.0f;
-    T *dst = reinterpret_cast<T *>(out + (long long)fr * NP * 1024) + l * 8 + j;
-    T hi;
-    StoreT<T>::store(&hi, v);
-    dst[0] = hi;
-    if constexpr (NP == 2) StoreT<T>::store(dst + 512, v - StoreT<T>::load(&hi));
-    if (e < C7_COUT) reinterpret_cast<float *>(out + (long long)C7_STEPS * 4 * NP * 1024)[e] = bias[e];
+    pack_store<T, NP>(out, fr, l, j, v);
+    if (e < C7_COUT) reinterpret_cast<float *>(out + (long long)C7_STEPS * 4 * NP * kFragBytes)[e] = bias[e];
 }
 
 size_t conv7_packed_bytes(int dtype) {
-    return (size_t)C7_STEPS * 4 * (dtype == DVC_F32 ? 2 : 1) * 1024 + C7_COUT * sizeof(float);
+    return (size_t)C7_STEPS * 4 * pieces_of(dtype) * kFragBytes + C7_COUT * sizeof(float);
 }
 
 hipError_t launch_conv7_pack(const float *w, const float *bias, void *packed, int dtype, hipStream_t s) {
     const unsigned blocks = C7_STEPS * 4 * 512 / 256;
     unsigned char *out = static_cast<unsigned char *>(packed);
-    if (dtype == DVC_F32) k_conv7_pack<bf16_t, 2><<<blocks, 256, 0, s>>>(w, bias, out);
-    else if (dtype == DVC_BF16) k_conv7_pack<bf16_t, 1><<<blocks, 256, 0, s>>>(w, bias, out);
-    else k_conv7_pack<f16_t, 1><<<blocks, 256, 0, s>>>(w, bias, out);
+    with_precision(dtype, [&](auto t, auto np) {
+        k_conv7_pack<decltype(t), decltype(np)::value><<<blocks, 256, 0, s>>>(w, bias, out);
+    });
     return hipGetLastError();
 }
 
@@ -468,9 +400,9 @@ hipError_t launch_conv7_flow(const float *flow, const void *packed, float *dst, 
     A.B = B; A.H = H; A.W = W; A.D = D;
     A.nth = (H + C7_TH - 1) / C7_TH; A.ntw = (W + C7_TW - 1) / C7_TW; A.ntd = (D + C7_TD - 1) / C7_TD;
     const unsigned grid = (unsigned)((long long)B * A.nth * A.ntw * A.ntd);
-    if (dtype == DVC_F32) k_conv7_flow<bf16_t, 2><<<grid, 256, 0, s>>>(A);
-    else if (dtype == DVC_BF16) k_conv7_flow<bf16_t, 1><<<grid, 256, 0, s>>>(A);
-    else k_conv7_flow<f16_t, 1><<<grid, 256, 0, s>>>(A);
+    with_precision(dtype, [&](auto t, auto np) {
+        k_conv7_flow<decltype(t), decltype(np)::value><<<grid, 256, 0, s>>>(A);
+    });
     return hipGetLastError();
 }
 

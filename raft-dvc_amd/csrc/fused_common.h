@@ -6,11 +6,6 @@
 
 namespace dvc {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ int buni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ long long buni64(long long v) {
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);

@@ -46,9 +46,6 @@
 
 namespace dvc {
 
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 // Window rows hold NW + 2 bf16 starting at an EVEN offset from the union's z start (st = iv or iv - 1),
 // so the MFMA epilogue writes value PAIRS (4-byte stores, one predicate per pair) and phase 2 realigns
 // the run by 0 or 16 bits.  Phase 2 keeps window planes 0 and 1 in registers from the start (each

@@ -32,9 +32,6 @@
 
 namespace dvc {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 template <int R> struct FusedCfg {
     static constexpr int n = 2 * R + 1;
     static constexpr int NW = 2 * R + 2;

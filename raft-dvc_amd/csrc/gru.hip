@@ -32,14 +32,9 @@
 //
 // LDS: 256 rows x 80 bytes (64 + 16: the 16 lanes of a b128 read land on distinct banks) per piece: 20 KB, 40 KB
 // for fp32.
-#include "common.h"
-
-#include <type_traits>
+#include "mfma_conv.h"
 
 namespace dvc {
-
-typedef float gf4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int GRU_S = DVC_GRU_SEG;      // output positions per workgroup
 constexpr int GRU_HID = DVC_GRU_HIDDEN; // hidden channels
@@ -67,28 +62,11 @@ __device__ __forceinline__ bool gru_line(const GruArgs &A, int n, int &b, long l
     return true;
 }
 
-template <typename T> __device__ __forceinline__ gf4 gru_mma(u32x4 a, u32x4 b, gf4 c);
-template <> __device__ __forceinline__ gf4 gru_mma<bf16_t>(u32x4 a, u32x4 b, gf4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
-                                                   0, 0);
-}
-template <> __device__ __forceinline__ gf4 gru_mma<f16_t>(u32x4 a, u32x4 b, gf4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
-                                                  0);
-}
-
-// two fp32 values -> one dword of 16-bit hi pieces and (NP = 2) one of lo pieces
-template <typename T, int NP> __device__ __forceinline__ void gru_split2(float a, float b, unsigned &hi, unsigned &lo) {
-    hi = pack2_16<T>(a, b);
-    lo = 0u;
-    if constexpr (NP == 2) lo = pack2_16<T>(a - bits16_to_f32<T>(hi), b - bits16_to_f32<T>(hi >> 16));
-}
-
 __device__ __forceinline__ float gru_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 template <typename T, int NP>
 __global__ __launch_bounds__(256, 1) void k_sep_gru_pass(GruArgs A) {
-    constexpr int S = GRU_S, PB = (S + 4) / 4, ROWB = 80, PIECE = 16 * (S + 8) * ROWB;
+    constexpr int S = GRU_S, PB = (S + 4) / 4, ROWB = kRowBytes, PIECE = 16 * (S + 8) * ROWB;
     static_assert(S == 8, "256 threads stage (S + 8) positions x 16 lines, one voxel each");
     __shared__ __attribute__((aligned(16))) unsigned char smem[NP * PIECE];
     const int tid = threadIdx.x, lane = tid & 63, m16 = lane & 15, h4 = lane >> 4;
@@ -118,8 +96,8 @@ __global__ __launch_bounds__(256, 1) void k_sep_gru_pass(GruArgs A) {
     float *mo = A.out + (long long)mb * GRU_HID * HWD + moff;
 
     const unsigned char *w1 = A.w + lane * 16;
-    const unsigned char *w2 = w1 + (long long)GRU_UNITS1 * 6 * NP * 1024;
-    const float *bias = reinterpret_cast<const float *>(A.w + (long long)GRU_FRAGS * NP * 1024);
+    const unsigned char *w2 = w1 + (long long)GRU_UNITS1 * 6 * NP * kFragBytes;
+    const float *bias = reinterpret_cast<const float *>(A.w + (long long)GRU_FRAGS * NP * kFragBytes);
 
     float st[32];   // staging registers: one voxel's 32 channels, or the owner's h values of an r h chunk
     auto stage_load = [&](int c) __attribute__((always_inline)) {   // chunk c of cat[h, x]
@@ -131,27 +109,11 @@ __global__ __launch_bounds__(256, 1) void k_sep_gru_pass(GruArgs A) {
             st[k] = ok ? *p : 0.0f;
         }
     };
-    auto stage_write = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            unsigned hi[4], lo[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) gru_split2<T, NP>(st[8 * o + 2 * j], st[8 * o + 2 * j + 1], hi[j], lo[j]);
-            *reinterpret_cast<u32x4 *>(srow + o * 16) = u32x4{hi[0], hi[1], hi[2], hi[3]};
-            if constexpr (NP == 2) *reinterpret_cast<u32x4 *>(srow + PIECE + o * 16) = u32x4{lo[0], lo[1], lo[2], lo[3]};
-        }
-    };
+    auto stage_write = [&]() __attribute__((always_inline)) { stage_row<T, NP>(st, srow, PIECE); };
 
     u32x4 wc[6][NP], wn[6][NP];
-    auto loadw = [&](const unsigned char *wb, int u, int nunits, u32x4 (&wf)[6][NP]) __attribute__((always_inline)) {
-        const unsigned char *p = wb + (long long)(u < nunits ? u : nunits - 1) * 6 * NP * 1024;
-#pragma unroll
-        for (int t = 0; t < 6; ++t)
-#pragma unroll
-            for (int pc = 0; pc < NP; ++pc) wf[t][pc] = *reinterpret_cast<const u32x4 *>(p + (t * NP + pc) * 1024);
-    };
     // the MFMAs of one staged chunk: five taps x NH halves of six tiles; pv[i] = position i of this wave takes part
-    auto chunk_mfma = [&](auto nh_c, gf4 (&acc)[6 * decltype(nh_c)::value][PB], const unsigned char *wb, int &u,
+    auto chunk_mfma = [&](auto nh_c, f32x4 (&acc)[6 * decltype(nh_c)::value][PB], const unsigned char *wb, int &u,
                           int nunits, const bool (&pv)[PB]) __attribute__((always_inline)) {
         constexpr int NH = decltype(nh_c)::value;
 #pragma unroll
@@ -166,19 +128,12 @@ __global__ __launch_bounds__(256, 1) void k_sep_gru_pass(GruArgs A) {
 #pragma unroll
             for (int hf = 0; hf < NH; ++hf) {
                 ++u;
-                loadw(wb, u, nunits, wn);   // the next unit's fragments, in flight under this unit's MFMAs
+                load_frags(wb, u, nunits, 6, wn);   // the next unit's fragments, in flight under this unit's MFMAs
 #pragma unroll
                 for (int tl = 0; tl < 6; ++tl)
 #pragma unroll
                     for (int i = 0; i < PB; ++i)
-                        if (pv[i]) {
-                            gf4 d = acc[hf * 6 + tl][i];
-                            if constexpr (NP == 2) {
-                                d = gru_mma<T>(wc[tl][1], bf[i][0], d);
-                                d = gru_mma<T>(wc[tl][0], bf[i][1], d);
-                            }
-                            acc[hf * 6 + tl][i] = gru_mma<T>(wc[tl][0], bf[i][0], d);
-                        }
+                        if (pv[i]) acc[hf * 6 + tl][i] = mma_step<T, NP>(wc[tl], bf[i], acc[hf * 6 + tl][i]);
 #pragma unroll
                 for (int tl = 0; tl < 6; ++tl)
 #pragma unroll
@@ -188,16 +143,16 @@ __global__ __launch_bounds__(256, 1) void k_sep_gru_pass(GruArgs A) {
     };
 
     // ---------------- phase 1: z and r at positions seg0 - 2 + (PB wave + i) ----------------
-    gf4 zg[6][PB], rg[6][PB];
+    f32x4 zg[6][PB], rg[6][PB];
     {
-        gf4 acc[12][PB];
+        f32x4 acc[12][PB];
 #pragma unroll
         for (int t = 0; t < 12; ++t)
 #pragma unroll
-            for (int i = 0; i < PB; ++i) acc[t][i] = gf4{0.f, 0.f, 0.f, 0.f};
+            for (int i = 0; i < PB; ++i) acc[t][i] = f32x4{0.f, 0.f, 0.f, 0.f};
         const bool all[PB] = {true, true, true};
         int u = 0;
-        loadw(w1, 0, GRU_UNITS1, wc);
+        load_frags(w1, 0, GRU_UNITS1, 6, wc);
         stage_load(0);
 #pragma unroll 1
         for (int c = 0; c < GRU_NCH; ++c) {
@@ -229,13 +184,13 @@ __global__ __launch_bounds__(256, 1) void k_sep_gru_pass(GruArgs A) {
         pv[i] = q >= 0 && q < S;
         ppos[i] = seg0 + q;
     }
-    gf4 acq[6][PB];
+    f32x4 acq[6][PB];
 #pragma unroll
     for (int t = 0; t < 6; ++t)
 #pragma unroll
-        for (int i = 0; i < PB; ++i) acq[t][i] = gf4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < PB; ++i) acq[t][i] = f32x4{0.f, 0.f, 0.f, 0.f};
     int u = 0;
-    loadw(w2, 0, GRU_UNITS2, wc);
+    load_frags(w2, 0, GRU_UNITS2, 6, wc);
     // h of this lane's 2 x PB x 4 values of r h chunk c (tiles 2c, 2c + 1): zero outside the volume
     auto rh_load = [&](int c) __attribute__((always_inline)) {
 #pragma unroll
@@ -258,8 +213,8 @@ __global__ __launch_bounds__(256, 1) void k_sep_gru_pass(GruArgs A) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) v[k] = rg[2 * c + tt][i][k] * st[(tt * PB + i) * 4 + k];
                 unsigned h0, l0, h1, l1;
-                gru_split2<T, NP>(v[0], v[1], h0, l0);
-                gru_split2<T, NP>(v[2], v[3], h1, l1);
+                split2<T, NP>(v[0], v[1], h0, l0);
+                split2<T, NP>(v[2], v[3], h1, l1);
                 unsigned char *d = smem + ((PB * wave + i + 2) * 16 + m16) * ROWB + tt * 32 + h4 * 8;
                 *reinterpret_cast<u32x2 *>(d) = u32x2{h0, h1};
                 if constexpr (NP == 2) *reinterpret_cast<u32x2 *>(d + PIECE) = u32x2{l0, l1};
@@ -316,7 +271,8 @@ __global__ __launch_bounds__(256) void k_gru_pack(const float *__restrict__ wz, 
                                                   unsigned char *__restrict__ out, int Cx) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= GRU_FRAGS * 512) return;
-    const int j = e & 7, l = (e >> 3) & 63, fr = e >> 9;
+    int fr, l, j;
+    frag_elem(e, fr, l, j);
     const float *w;
     int tile, ct;
     if (fr < GRU_UNITS1 * 6) {
@@ -333,28 +289,24 @@ __global__ __launch_bounds__(256) void k_gru_pack(const float *__restrict__ wz, 
     const int c = ct / 5, t = ct % 5;
     const int o = 16 * tile + (l & 15), kp = 32 * c + 8 * (l >> 4) + j, cin = GRU_HID + Cx;
     const float v = kp < cin ? w[((long long)o * cin + kp) * 5 + t] : 0.0f;
-    T *dst = reinterpret_cast<T *>(out + (long long)fr * NP * 1024) + l * 8 + j;
-    T hi;
-    StoreT<T>::store(&hi, v);
-    dst[0] = hi;
-    if constexpr (NP == 2) StoreT<T>::store(dst + 512, v - StoreT<T>::load(&hi));
+    pack_store<T, NP>(out, fr, l, j, v);
     if (e < 3 * GRU_HID) {
-        float *b = reinterpret_cast<float *>(out + (long long)GRU_FRAGS * NP * 1024);
+        float *b = reinterpret_cast<float *>(out + (long long)GRU_FRAGS * NP * kFragBytes);
         b[e] = e < GRU_HID ? bz[e] : e < 2 * GRU_HID ? br[e - GRU_HID] : bq[e - 2 * GRU_HID];
     }
 }
 
 size_t gru_packed_bytes(int dtype) {
-    return (size_t)GRU_FRAGS * (dtype == DVC_F32 ? 2 : 1) * 1024 + 3 * GRU_HID * sizeof(float);
+    return (size_t)GRU_FRAGS * pieces_of(dtype) * kFragBytes + 3 * GRU_HID * sizeof(float);
 }
 
 hipError_t launch_gru_pack(const float *wz, const float *wr, const float *wq, const float *bz, const float *br,
                            const float *bq, void *packed, int Cx, int dtype, hipStream_t s) {
     const unsigned blocks = GRU_FRAGS * 512 / 256;
     unsigned char *out = static_cast<unsigned char *>(packed);
-    if (dtype == DVC_F32) k_gru_pack<bf16_t, 2><<<blocks, 256, 0, s>>>(wz, wr, wq, bz, br, bq, out, Cx);
-    else if (dtype == DVC_BF16) k_gru_pack<bf16_t, 1><<<blocks, 256, 0, s>>>(wz, wr, wq, bz, br, bq, out, Cx);
-    else k_gru_pack<f16_t, 1><<<blocks, 256, 0, s>>>(wz, wr, wq, bz, br, bq, out, Cx);
+    with_precision(dtype, [&](auto t, auto np) {
+        k_gru_pack<decltype(t), decltype(np)::value><<<blocks, 256, 0, s>>>(wz, wr, wq, bz, br, bq, out, Cx);
+    });
     return hipGetLastError();
 }
 
@@ -370,9 +322,9 @@ hipError_t launch_sep_gru_pass(const float *h, const float *x, const void *packe
     A.per_b = (int)(A.HWD / A.len);
     A.nlines = B * A.per_b;
     const unsigned grid = (unsigned)((A.nlines + 15) / 16) * (unsigned)((A.len + GRU_S - 1) / GRU_S);
-    if (dtype == DVC_F32) k_sep_gru_pass<bf16_t, 2><<<grid, 256, 0, s>>>(A);
-    else if (dtype == DVC_BF16) k_sep_gru_pass<bf16_t, 1><<<grid, 256, 0, s>>>(A);
-    else k_sep_gru_pass<f16_t, 1><<<grid, 256, 0, s>>>(A);
+    with_precision(dtype, [&](auto t, auto np) {
+        k_sep_gru_pass<decltype(t), decltype(np)::value><<<grid, 256, 0, s>>>(A);
+    });
     return hipGetLastError();
 }
 

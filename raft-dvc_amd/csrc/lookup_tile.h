@@ -145,19 +145,12 @@ __device__ __forceinline__ void lds_run(const unsigned char *base, int addr, con
     for (int i = 0; i < NW; ++i) v[i] = p[i];
 }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 // z-lerped run of one window column: zl[v] = fma(R[v+1], w1[v], R[v] * w0[v]), v < n,
 // kept as n/2 pairs (packed-f32 math, same per-element rounding) plus a tail.
 template <int n> struct ZRun {
     f32x2 p[n / 2];
     float t;
 };
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // convc1 fusion (PROJ): the motion encoder's first layer, relu(conv1x1(corr, W) + b)
 // with 96 output channels (reference src/core/update.py:219-222, 246), applied to the

@@ -400,10 +400,14 @@ def flow_step(coords1: torch.Tensor, delta_flow, target_shape):
     return new, up
 
 
-__all__ = ["pack_queries", "pack_targets", "pack_targets_gathered", "build", "pool", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "sample3d",
-           "proj_pack", "proj_pack_cached", "lookup_proj",
-           "coords_grid", "upflow", "flow_step",
-           "fused_workspace", "dtype_code", "layout", "bricked_levels", "DVC_BRICKED", "_lib"]
+def _nbytes(t: torch.Tensor) -> int:
+    return t.numel() * t.element_size()
+
+
+def _check_packed(what: str, packed: torch.Tensor, need: int, hint: str) -> None:
+    """A packed-weights buffer has the byte count its kernel will read (need = 0: no kernel for these shapes)."""
+    if need == 0 or _nbytes(packed) != need:
+        raise ValueError(f"{what}: packed weights of {_nbytes(packed)} bytes; {hint}")
 
 
 _GRU_AXES = ("h", "w", "d")
@@ -447,18 +451,13 @@ def sep_gru(h: torch.Tensor, x: torch.Tensor, packed: torch.Tensor, dtype: int) 
     _need_cuda(h, x, packed)
     h, x = _f32c(h), _f32c(x)
     need = 3 * lib().dvc_gru_packed_bytes(h.shape[1], x.shape[1], dtype)
-    if need == 0 or packed.numel() * packed.element_size() != need:
-        raise ValueError(f"sep_gru: packed weights of {packed.numel() * packed.element_size()} bytes; hidden "
-                         f"{h.shape[1]}, input {x.shape[1]} and this precision take {need} (gru_pack with the same dtype)")
+    _check_packed("sep_gru", packed, need, f"hidden {h.shape[1]}, input {x.shape[1]} and this precision take {need} "
+                  "(gru_pack with the same dtype)")
     a, b = torch.empty_like(h), torch.empty_like(h)
     sep_gru_pass(h, x, packed[0], a, 0, dtype)
     sep_gru_pass(a, x, packed[1], b, 1, dtype)
     sep_gru_pass(b, x, packed[2], a, 2, dtype)
     return a
-
-
-def _nbytes(t: torch.Tensor) -> int:
-    return t.numel() * t.element_size()
 
 
 def _conv_operand(t: torch.Tensor, what: str) -> None:
@@ -500,9 +499,8 @@ def conv3(src0: torch.Tensor, src1, packed: torch.Tensor, dst: torch.Tensor, dst
     B, c0, H, W, D = src0.shape
     c1 = 0 if src1 is None else int(src1.shape[1])
     need = lib().dvc_conv3_packed_bytes(c0 + c1, cout, dtype)
-    if need == 0 or _nbytes(packed) != need:
-        raise ValueError(f"conv3: packed weights of {_nbytes(packed)} bytes; cin {c0 + c1}, cout {cout} and this "
-                         f"precision take {need} (conv3_pack with the same dtype)")
+    _check_packed("conv3", packed, need, f"cin {c0 + c1}, cout {cout} and this precision take {need} "
+                  "(conv3_pack with the same dtype)")
     check(lib().dvc_conv3(_ptr(src0), c0, None if src1 is None else _ptr(src1), c1, _ptr(packed), _ptr(dst),
                           int(dst.shape[1]), int(dst_offset), int(cout), int(bool(relu)), B, H, W, D, dtype,
                           _stream(src0)), "conv3")
@@ -537,9 +535,13 @@ def conv7_flow(flow: torch.Tensor, packed: torch.Tensor, dst: torch.Tensor, dtyp
         raise ValueError(f"conv7_flow: flow must be (B, 3, H, W, D) and dst (B, {_lib.CONV7_COUT}, H, W, D); got "
                          f"{tuple(flow.shape)} and {tuple(dst.shape)}")
     need = lib().dvc_conv7_flow_packed_bytes(dtype)
-    if need == 0 or _nbytes(packed) != need:
-        raise ValueError(f"conv7_flow: packed weights of {_nbytes(packed)} bytes; this precision takes {need} "
-                         "(conv7_flow_pack with the same dtype)")
+    _check_packed("conv7_flow", packed, need, f"this precision takes {need} (conv7_flow_pack with the same dtype)")
     B, _, H, W, D = flow.shape
     check(lib().dvc_conv7_flow(_ptr(flow), _ptr(packed), _ptr(dst), B, H, W, D, dtype, _stream(flow)), "conv7_flow")
     return dst
+
+
+__all__ = ["pack_queries", "pack_targets", "pack_targets_gathered", "build", "pool", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "sample3d",
+           "proj_pack", "proj_pack_cached", "lookup_proj",
+           "coords_grid", "upflow", "flow_step",
+           "fused_workspace", "dtype_code", "layout", "bricked_levels", "DVC_BRICKED", "_lib"]
