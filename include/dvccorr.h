@@ -342,6 +342,41 @@ int dvc_conv7_flow_pack(const float *w, const float *bias, void *packed, int dty
 int dvc_conv7_flow(const float *flow, const void *packed, float *dst, int B, int H, int W, int D, int dtype,
                    void *stream);
 
+/* The backward of dvc_conv3 (csrc/conv3_grad.hip).  With y = conv(cat[src0, src1], w) + bias (+ ReLU) and
+ * g = dL/dy (times [y > 0] under ReLU), all (B, C, H, W, D) float32, contiguous:
+ *   dvc_conv3_grad_prep   g = grad_y [y > 0] and db[o] = sum over (b, v) of g[b, o, v].  With ReLU pass y (the
+ *               layer's own output) and g; without, pass both NULL: g is grad_y itself and only db is written.
+ *               partial is a work buffer of cout * B * ceil(H W D / DVC_CONV3_PREP_CHUNK) floats; the sums have a
+ *               fixed order, so db is bit-identical from run to run.  g must not overlap grad_y or y.
+ *   dvc_conv3_pack_dgrad  the weights of the input gradient: the fragments of the layer W'[ci][o][t'] =
+ *               w[o][ci][26 - t'] (cin and cout swapped, all three axes flipped, zero biases) in dvc_conv3_pack's
+ *               layout, dvc_conv3_packed_bytes(cout, cin, dtype) bytes, so that
+ *               dvc_conv3(g, cout, NULL, 0, packed, dx, cin, 0, cin, 0, ...) is d loss / d cat[src0, src1].
+ *   dvc_conv3_wgrad       dw[o][ci][t] = sum over (b, v) of g[b, o, v] cat[src0, src1][b, ci, v + delta(t)], the
+ *               (cout, c0 + c1, 3, 3, 3) float32 weight gradient, as a GEMM over the voxels on the matrix cores.  A
+ *               K-block is a box of DVC_CONV3_WGRAD_KH x KW x KD voxels; the nbox = B ceil(H / KH) ceil(W / KW)
+ *               ceil(D / KD) blocks are cut into slabs of per = ceil(nbox / min(nbox, ceil(DVC_CONV3_WGRAD_TARGET /
+ *               (ceil(cin / 16) * groups)))) consecutive blocks, groups = ceil(cout / 32) (1 for cout <= 16).  Each
+ *               of the ceil(nbox / per) slabs writes its partial dw to the workspace and the slabs are summed in index
+ *               order (no slab is empty; bit-identical from run to run).  dw and the workspace must not overlap an
+ *               input.  dtype as dvc_conv3; for DVC_F16 the gradient operand g is rounded to fp16 too (scale the
+ *               loss as under AMP).
+ *   dvc_conv3_wgrad_workspace_bytes   slabs * cout * cin * 27 * 4 (0 for an unsupported shape).
+ * No atomics, no allocation, no host synchronisation.  Errors as dvc_conv3: a null pointer, B / H / W / D < 1, a bad
+ * dtype, channel counts < 1 or overlapping buffers are DVC_ERR_INVALID; cin or cout above 128 or 2^31 voxels or more
+ * are DVC_ERR_UNSUPPORTED. */
+#define DVC_CONV3_WGRAD_KH 4
+#define DVC_CONV3_WGRAD_KW 4
+#define DVC_CONV3_WGRAD_KD 16
+#define DVC_CONV3_WGRAD_TARGET 512
+#define DVC_CONV3_PREP_CHUNK 4096
+int dvc_conv3_pack_dgrad(const float *w, void *packed, int cin, int cout, int dtype, void *stream);
+int dvc_conv3_grad_prep(const float *grad_y, const float *y_or_null, float *g_or_null, float *db, float *partial,
+                        int cout, int B, int H, int W, int D, void *stream);
+size_t dvc_conv3_wgrad_workspace_bytes(int cin, int cout, int B, int H, int W, int D);
+int dvc_conv3_wgrad(const float *src0, int c0, const float *src1, int c1, const float *g, int cout, float *dw,
+                    void *workspace, int B, int H, int W, int D, int dtype, void *stream);
+
 /* Diagnostics hook for A/B timing.  The product kernel selection is a fixed table;
  * an override set here is PROCESS-GLOBAL (round 6; it was thread-local, which a
  * backward run on the autograd engine's worker thread never saw): it changes every

@@ -81,6 +81,12 @@ hipError_t launch_conv3_pack(const float *w, const float *bias, void *packed, in
 hipError_t launch_conv3(const float *src0, int c0, const float *src1, int c1, const void *packed, float *dst,
                         int dst_channels, int dst_offset, int cout, int relu, int B, int H, int W, int D, int dtype,
                         hipStream_t s);
+size_t conv3_wgrad_workspace_bytes(int cin, int cout, int B, int H, int W, int D);
+hipError_t launch_conv3_pack_dgrad(const float *w, void *packed, int cin, int cout, int dtype, hipStream_t s);
+hipError_t launch_conv3_grad_prep(const float *grad_y, const float *y, float *g, float *db, float *partial, int cout,
+                                  int B, int H, int W, int D, hipStream_t s);
+hipError_t launch_conv3_wgrad(const float *src0, int c0, const float *src1, int c1, const float *g, int cout, float *dw,
+                              void *workspace, int B, int H, int W, int D, int dtype, hipStream_t s);
 size_t conv7_packed_bytes(int dtype);
 hipError_t launch_conv7_pack(const float *w, const float *bias, void *packed, int dtype, hipStream_t s);
 hipError_t launch_conv7_flow(const float *flow, const void *packed, float *dst, int B, int H, int W, int D, int dtype,
@@ -1258,6 +1264,57 @@ int dvc_conv3(const float *src0, int c0, const float *src1, int c1, const void *
         return fail(DVC_ERR_INVALID, "conv3: dst must not overlap a source (a voxel reads its neighbours)");
     return launched("conv3", launch_conv3(src0, c0, src1, c1, packed, dst, dst_channels, dst_offset, cout, relu != 0, B,
                                           H, W, D, dtype, (hipStream_t)stream));
+}
+
+// the backward of dvc_conv3 (conv3_grad.hip)
+int dvc_conv3_pack_dgrad(const float *w, void *packed, int cin, int cout, int dtype, void *stream) {
+    if (!w || !packed) return fail(DVC_ERR_INVALID, "conv3_pack_dgrad: null pointer");
+    if (int rc = conv3_shape_check("conv3_pack_dgrad", cin, cout, dtype)) return rc;
+    return launched("conv3_pack_dgrad", launch_conv3_pack_dgrad(w, packed, cin, cout, dtype, (hipStream_t)stream));
+}
+
+int dvc_conv3_grad_prep(const float *grad_y, const float *y_or_null, float *g_or_null, float *db, float *partial,
+                        int cout, int B, int H, int W, int D, void *stream) {
+    if (!grad_y || !db || !partial) return fail(DVC_ERR_INVALID, "conv3_grad_prep: null pointer");
+    if (!y_or_null != !g_or_null)
+        return fail(DVC_ERR_INVALID, "conv3_grad_prep: y and g go together (both for ReLU, neither without)");
+    if (int rc = volume_check("conv3_grad_prep", B, H, W, D)) return rc;
+    if (int rc = conv3_shape_check("conv3_grad_prep", 1, cout, DVC_F32)) return rc;
+    const size_t nb = (size_t)B * H * W * D * cout * 4;
+    if (overlaps(g_or_null, nb, grad_y, nb) || overlaps(g_or_null, nb, y_or_null, nb))
+        return fail(DVC_ERR_INVALID, "conv3_grad_prep: g must not overlap grad_y or y");
+    return launched("conv3_grad_prep", launch_conv3_grad_prep(grad_y, y_or_null, g_or_null, db, partial, cout, B, H, W,
+                                                              D, (hipStream_t)stream));
+}
+
+size_t dvc_conv3_wgrad_workspace_bytes(int cin, int cout, int B, int H, int W, int D) {
+    if (conv3_shape_check("conv3_wgrad_workspace_bytes", cin, cout, DVC_F32)) return 0;
+    if (volume_check("conv3_wgrad_workspace_bytes", B, H, W, D)) return 0;
+    return conv3_wgrad_workspace_bytes(cin, cout, B, H, W, D);
+}
+
+int dvc_conv3_wgrad(const float *src0, int c0, const float *src1, int c1, const float *g, int cout, float *dw,
+                    void *workspace, int B, int H, int W, int D, int dtype, void *stream) {
+    if (!src0 || !g || !dw || !workspace) return fail(DVC_ERR_INVALID, "conv3_wgrad: null pointer");
+    if (int rc = volume_check("conv3_wgrad", B, H, W, D)) return rc;
+    if (!src1) c1 = 0;
+    if (c0 < 1 || c1 < 0 || (src1 && c1 < 1)) return fail(DVC_ERR_INVALID, "conv3_wgrad: c0=%d c1=%d", c0, c1);
+    if (c0 > DVC_CONV3_MAX_CIN || c1 > DVC_CONV3_MAX_CIN)
+        return fail(DVC_ERR_UNSUPPORTED, "conv3_wgrad: c0=%d c1=%d (the kernel covers c0 + c1 <= %d)", c0, c1,
+                    DVC_CONV3_MAX_CIN);
+    if (int rc = conv3_shape_check("conv3_wgrad", c0 + c1, cout, dtype)) return rc;
+    const size_t vox = (size_t)B * H * W * D * 4, dwb = (size_t)cout * (c0 + c1) * 27 * 4;
+    const size_t wsb = conv3_wgrad_workspace_bytes(c0 + c1, cout, B, H, W, D);
+    const void *outs[2] = {dw, workspace};
+    const size_t outb[2] = {dwb, wsb};
+    for (int i = 0; i < 2; ++i)
+        if (overlaps(outs[i], outb[i], src0, vox * c0) || (src1 && overlaps(outs[i], outb[i], src1, vox * c1)) ||
+            overlaps(outs[i], outb[i], g, vox * cout))
+            return fail(DVC_ERR_INVALID, "conv3_wgrad: dw and the workspace must not overlap an input");
+    if (overlaps(dw, dwb, workspace, wsb))
+        return fail(DVC_ERR_INVALID, "conv3_wgrad: dw must not overlap the workspace");
+    return launched("conv3_wgrad", launch_conv3_wgrad(src0, c0, src1, c1, g, cout, dw, workspace, B, H, W, D, dtype,
+                                                      (hipStream_t)stream));
 }
 
 size_t dvc_conv7_flow_packed_bytes(int dtype) {

@@ -199,31 +199,15 @@ __global__ __launch_bounds__(256, 1) void k_conv3_mfma(Conv3Args A) {
     }
 }
 
-// Packed weights: fragment ((chunk c, tap t = (kh 3 + kw) 3 + kd), tile), NP pieces of [lane][8] 16-bit values each:
-// lane l element j = weight [o = 16 tile + (l & 15)][input channel 32 c + 8 (l >> 4) + j][t], zero where o >= cout or
-// the channel >= cin; then 16 nt float32 biases (zero past cout).
+// Packed weights (conv3_pack_elem, mfma_conv.h): fragment ((chunk c, tap t = (kh 3 + kw) 3 + kd), tile), NP pieces of
+// [lane][8] 16-bit values each: lane l element j = weight [o = 16 tile + (l & 15)][input channel 32 c + 8 (l >> 4) + j][t],
+// zero where o >= cout or the channel >= cin; then 16 nt float32 biases (zero past cout).
 template <typename T, int NP>
 __global__ __launch_bounds__(256) void k_conv3_pack(const float *__restrict__ w, const float *__restrict__ bias,
                                                     unsigned char *__restrict__ out, int cin, int cout, int nch, int nt) {
-    const int nfr = nch * 27 * nt;
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= nfr * 512) return;
-    int fr, l, j;
-    frag_elem(e, fr, l, j);
-    const int tile = fr % nt, ct = fr / nt, c = ct / 27, t = ct - 27 * c;
-    const int o = 16 * tile + (l & 15), kp = 32 * c + 8 * (l >> 4) + j;
-    const float v = o < cout && kp < cin ? w[((long long)o * cin + kp) * 27 + t] : 0.0f;
-    pack_store<T, NP>(out, fr, l, j, v);
-    if (e < 16 * nt) {
-        float *bo = reinterpret_cast<float *>(out + (long long)nfr * NP * kFragBytes);
-        bo[e] = e < cout ? bias[e] : 0.0f;
-    }
-}
-
-// packed tiles of an output channel count: 4 FULL + SHARED of the instance that runs it
-static int conv3_tiles(int cout) {
-    const int n = (cout + 15) / 16;
-    return n <= 2 ? n : n <= 4 ? 4 : n == 5 ? 5 : 8;
+    conv3_pack_elem<T, NP>(blockIdx.x * 256 + threadIdx.x, out, cin, cout, nch, nt,
+                           [&](int o, int kp, int t) { return w[((long long)o * cin + kp) * 27 + t]; },
+                           [&](int o) { return bias[o]; });
 }
 
 size_t conv3_packed_bytes(int cin, int cout, int dtype) {

@@ -94,6 +94,29 @@ __device__ __forceinline__ void pack_store(unsigned char *out, int fr, int l, in
     if constexpr (NP == 2) StoreT<T>::store(dst + kFragBytes / 2, v - StoreT<T>::load(&hi));
 }
 
+// packed tiles of a 3 x 3 x 3 layer's output channel count: 4 FULL + SHARED of the k_conv3_mfma instance that runs it
+inline int conv3_tiles(int cout) {
+    const int n = (cout + 15) / 16;
+    return n <= 2 ? n : n <= 4 ? 4 : n == 5 ? 5 : 8;
+}
+
+// Element e of a 3 x 3 x 3 layer's packed weights (k_conv3_pack, k_conv3_pack_dgrad): fragment ((chunk c, tap t = (kh 3
+// + kw) 3 + kd), tile), NP pieces of [lane][8] 16-bit values each: lane l element j = weight(o = 16 tile + (l & 15),
+// input channel 32 c + 8 (l >> 4) + j, t), zero where o >= cout or the channel >= cin; then 16 nt float32 biases
+// bias(o) (zero past cout).
+template <typename T, int NP, typename WF, typename BF>
+__device__ __forceinline__ void conv3_pack_elem(int e, unsigned char *out, int cin, int cout, int nch, int nt,
+                                                WF weight, BF bias) {
+    const int nfr = nch * 27 * nt;
+    if (e >= nfr * 512) return;
+    int fr, l, j;
+    frag_elem(e, fr, l, j);
+    const int tile = fr % nt, ct = fr / nt, c = ct / 27, t = ct - 27 * c;
+    const int o = 16 * tile + (l & 15), kp = 32 * c + 8 * (l >> 4) + j;
+    pack_store<T, NP>(out, fr, l, j, o < cout && kp < cin ? weight(o, kp, t) : 0.0f);
+    if (e < 16 * nt) reinterpret_cast<float *>(out + (long long)nfr * NP * kFragBytes)[e] = e < cout ? bias(e) : 0.0f;
+}
+
 // workgroup bid of a (B, nth, ntw, ntd) grid of TH x TW x TD output boxes -> batch element and box origin
 __device__ __forceinline__ void box_of_block(unsigned bid, int nth, int ntw, int ntd, int TH, int TW, int TD, int &b,
                                              int &h0, int &w0, int &d0) {

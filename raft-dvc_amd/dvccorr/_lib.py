@@ -33,6 +33,7 @@ EXPORTED = (
     "dvc_gru_packed_bytes", "dvc_gru_pack", "dvc_sep_gru_pass",
     "dvc_conv3_packed_bytes", "dvc_conv3_pack", "dvc_conv3",
     "dvc_conv7_flow_packed_bytes", "dvc_conv7_flow_pack", "dvc_conv7_flow",
+    "dvc_conv3_pack_dgrad", "dvc_conv3_grad_prep", "dvc_conv3_wgrad_workspace_bytes", "dvc_conv3_wgrad",
 )
 PROJ_COUT = 96          # DVC_PROJ_COUT (convc1 output channels, update.py:222)
 PROJ_MAX_RADIUS = 4     # DVC_PROJ_MAX_RADIUS
@@ -42,6 +43,11 @@ GRU_SEG = 8             # DVC_GRU_SEG: output positions along the conv axis per 
 CONV3_TH, CONV3_TW, CONV3_TD = 4, 4, 16     # DVC_CONV3_TH / TW / TD: output box of one k_conv3_mfma workgroup
 CONV3_MAX_CIN = 128     # DVC_CONV3_MAX_CIN
 CONV3_MAX_COUT = 128    # DVC_CONV3_MAX_COUT
+# DVC_CONV3_WGRAD_KH / KW / KD: the K-block (a voxel box) of k_conv3_wgrad; DVC_CONV3_WGRAD_TARGET: the workgroups the
+# slab rule aims for (ops.conv3_wgrad_slabs); DVC_CONV3_PREP_CHUNK: voxels per workgroup of k_conv3_grad_prep
+CONV3_WGRAD_KH, CONV3_WGRAD_KW, CONV3_WGRAD_KD = 4, 4, 16
+CONV3_WGRAD_TARGET = 512
+CONV3_PREP_CHUNK = 4096
 CONV7_TH, CONV7_TW, CONV7_TD = 4, 4, 16     # DVC_CONV7_TH / TW / TD: output box of one k_conv7_flow workgroup
 CONV7_COUT = 64         # DVC_CONV7_COUT (encoder.convf1, update.py:225)
 
@@ -118,6 +124,10 @@ def lib() -> ctypes.CDLL:
         "dvc_conv3_packed_bytes": (sz, [i32, i32, i32]),
         "dvc_conv3_pack": (i32, [vp, vp, vp, i32, i32, i32, vp]),
         "dvc_conv3": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "dvc_conv3_pack_dgrad": (i32, [vp, vp, i32, i32, i32, vp]),
+        "dvc_conv3_grad_prep": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+        "dvc_conv3_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
+        "dvc_conv3_wgrad": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp]),
         "dvc_conv7_flow_packed_bytes": (sz, [i32]),
         "dvc_conv7_flow_pack": (i32, [vp, vp, vp, i32, vp]),
         "dvc_conv7_flow": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),

@@ -25,6 +25,11 @@ the PyTorch dispatcher as named operators with shape functions:
                                                  3 x 3 x 3 conv of cat[src0, src1] + bias (+ ReLU)   update.py:226-251
     dvccorr::conv7_flow(flow, packed, dst, dtype)    dst = relu(convf1(flow))                         update.py:225, 247
 
+    dvccorr::conv3_ad(x, x2?, weight, bias, relu, dtype) -> y   the same layer as a differentiable op (update.py:226-251);
+        its registered backward is dvccorr::conv3_grad_prep(grad_y, y?, relu) -> (g, db), dvccorr::conv3_wgrad(x, x2?,
+        g, dtype) -> dW and dvccorr::conv3 on g with the transposed, flipped weights of dvccorr::conv3_pack_dgrad(weight,
+        dtype) (a cached pack, no compute)
+
 Every op runs the HIP kernels of libdvccorr.so through ops.py (no CPU
 fallback); the fake (meta) implementations only compute output shapes, so the
 ops trace under torch.compile / FakeTensorMode and torch.library.opcheck.
@@ -236,4 +241,126 @@ def _(flow, packed, dst, dtype):
     return None
 
 
-__all__ = ["sep_gru", "conv3", "conv7_flow", "build", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "lookup_ad", "lookup_convc1_ad"]
+# ---------------------------------------------------------------------------------------------------------------
+# a differentiable 3 x 3 x 3 layer (dvccorr.conv3x3x3_ad): forward k_conv3_mfma, backward csrc/conv3_grad.hip
+# ---------------------------------------------------------------------------------------------------------------
+_conv3_ad_packs = None
+
+
+def _conv3_packs():
+    """The module-level pack cache of conv3_ad: entries keyed (kind, weight / bias objects, precision), valid for the
+    tensors' version counters and storage (update._PackCache), so calls between optimiser steps do not re-pack."""
+    global _conv3_ad_packs
+    if _conv3_ad_packs is None:
+        from .update import _PackCache
+        _conv3_ad_packs = _PackCache()
+    return _conv3_ad_packs
+
+
+_CONV3_AD_MAX_PACKS = 64   # an entry keeps its weights alive: a cache past this many layers starts over
+
+
+def _conv3_packed(weight: Tensor, bias: Tensor, dtype: int) -> Tensor:
+    if len(_conv3_packs()._entries) > _CONV3_AD_MAX_PACKS:
+        _conv3_packs()._entries.clear()
+    return _conv3_packs().get(("fwd", id(weight), id(bias), dtype), (weight, bias),
+                              lambda: ops.conv3_pack(weight, bias, dtype))
+
+
+@torch.library.custom_op("dvccorr::conv3_pack_dgrad", mutates_args=())
+def conv3_pack_dgrad(weight: Tensor, dtype: int) -> Tensor:
+    """ops.conv3_pack_dgrad through the pack cache: the input gradient's weights, as an operator so that the backward
+    of dvccorr::conv3_ad traces."""
+    return _conv3_packs().get(("dgrad", id(weight), dtype), (weight,), lambda: ops.conv3_pack_dgrad(weight, dtype))
+
+
+@conv3_pack_dgrad.register_fake
+def _(weight, dtype):
+    # dvc_conv3_packed_bytes(cout, cin, dtype): the layer with the channel counts swapped
+    tiles, chunks = (weight.shape[1] + 15) // 16, (weight.shape[0] + 31) // 32
+    nt = tiles if tiles <= 2 else 4 if tiles <= 4 else 5 if tiles == 5 else 8
+    return weight.new_empty((chunks * 27 * nt * (2 if dtype == ops.DVC_F32 else 1) * 256 + 16 * nt,), dtype=_F32)
+
+
+@torch.library.custom_op("dvccorr::conv3_ad", mutates_args=())
+def conv3_ad(x: Tensor, x2: Optional[Tensor], weight: Tensor, bias: Tensor, relu: bool, dtype: int) -> Tensor:
+    """conv3x3x3(cat[x, x2]) + bias (+ ReLU) as a differentiable op: packs the weights (cached), allocates y and runs
+    dvc_conv3.  x, x2, weight and bias carry gradients."""
+    x = ops._f32c(x)
+    x2 = None if x2 is None else ops._f32c(x2)
+    y = torch.empty((x.shape[0], weight.shape[0]) + tuple(x.shape[2:]), dtype=_F32, device=x.device)
+    ops.conv3(x, x2, _conv3_packed(weight, bias, dtype), y, 0, int(weight.shape[0]), relu, dtype)
+    return y
+
+
+@conv3_ad.register_fake
+def _(x, x2, weight, bias, relu, dtype):
+    return x.new_empty((x.shape[0], weight.shape[0]) + tuple(x.shape[2:]), dtype=_F32)
+
+
+@torch.library.custom_op("dvccorr::conv3_grad_prep", mutates_args=())
+def conv3_grad_prep(grad_y: Tensor, y: Optional[Tensor], relu: bool) -> tuple[Tensor, Tensor]:
+    g, db = ops.conv3_grad_prep(grad_y, y, relu)
+    # an operator may not return an input: without ReLU the caller keeps grad_y (no copy) and g is empty
+    return (g if relu else grad_y.new_empty(0)), db
+
+
+@conv3_grad_prep.register_fake
+def _(grad_y, y, relu):
+    return (grad_y.new_empty(grad_y.shape if relu else (0,), dtype=_F32), grad_y.new_empty((grad_y.shape[1],), dtype=_F32))
+
+
+@torch.library.custom_op("dvccorr::conv3_wgrad", mutates_args=())
+def conv3_wgrad(x: Tensor, x2: Optional[Tensor], g: Tensor, dtype: int) -> Tensor:
+    return ops.conv3_wgrad(x, x2, g, dtype)
+
+
+@conv3_wgrad.register_fake
+def _(x, x2, g, dtype):
+    cin = x.shape[1] + (0 if x2 is None else x2.shape[1])
+    return x.new_empty((g.shape[1], cin, 3, 3, 3), dtype=_F32)
+
+
+def _conv3_ad_setup(ctx, inputs, output):
+    x, x2, weight, bias, relu, dtype = inputs
+    ctx.save_for_backward(x, x2, weight, output if relu else None)
+    ctx.cfg = (bool(relu), int(dtype))
+    ctx.meta = (x.dtype, None if x2 is None else x2.dtype, weight.dtype, tuple(bias.shape), bias.dtype)
+
+
+def _conv3_ad_backward(ctx, grad_y):
+    """g = dL/dy [y > 0] (the mask from the op's own stored output) and db in one pass (dvccorr::conv3_grad_prep);
+    dW on k_conv3_wgrad (dvccorr::conv3_wgrad); d cat[x, x2] as one dvccorr::conv3 launch of g with the transposed,
+    flipped weights, dx and dx2 its two channel ranges.  Whatever needs_input_grad does not ask for is skipped."""
+    if grad_y.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("dvccorr.conv3x3x3_ad has no double backward")
+    x, x2, weight, y = ctx.saved_tensors
+    relu, dtype = ctx.cfg
+    dtx, dtx2, dtw, sb, dtb = ctx.meta
+    need_x, need_x2, need_w, need_b = ctx.needs_input_grad[:4]
+    dx = dx2 = dw = db = None
+    if not (need_x or need_x2 or need_w or need_b):
+        return (None,) * 6
+    grad_y = ops._f32c(grad_y)
+    g, db_ = conv3_grad_prep(grad_y, y, relu)
+    if not relu:
+        g = grad_y
+    if need_b:
+        db = db_.reshape(sb).to(dtb)
+    if need_w:
+        dw = conv3_wgrad(ops._f32c(x), None if x2 is None else ops._f32c(x2), g, dtype).to(dtw)
+    if need_x or need_x2:
+        c0, cin, cout = int(x.shape[1]), int(weight.shape[1]), int(weight.shape[0])
+        dcat = torch.empty((g.shape[0], cin) + tuple(g.shape[2:]), dtype=_F32, device=g.device)
+        conv3(g, None, conv3_pack_dgrad(weight, dtype), dcat, 0, cin, False, dtype)
+        if need_x:
+            dx = dcat[:, :c0].to(dtx)
+        if need_x2:
+            dx2 = dcat[:, c0:].to(dtx2)
+    return dx, dx2, dw, db, None, None
+
+
+torch.library.register_autograd("dvccorr::conv3_ad", _conv3_ad_backward, setup_context=_conv3_ad_setup)
+
+
+__all__ = ["conv3_ad", "conv3_grad_prep", "conv3_wgrad", "conv3_pack_dgrad", "sep_gru", "conv3", "conv7_flow", "build", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "lookup_ad", "lookup_convc1_ad"]

@@ -20,6 +20,9 @@ straight to libdvccorr.so (no CPU fallback).  Shapes follow include/dvccorr.h:
     conv3_pack(weight (Co, Ci, 3, 3, 3), bias, dtype)  -> packed weights of one 3 x 3 x 3 convolution
     conv3(src0, src1 | None, packed, dst, offset, Co, relu, dtype) -> dst[:, offset:offset + Co] written  f32
     conv7_flow_pack(weight (64, 3, 7, 7, 7), bias, dtype) / conv7_flow(flow, packed, dst, dtype)   encoder.convf1
+    conv3_pack_dgrad(weight, dtype)                    -> packed weights of the layer's input gradient (run by conv3)
+    conv3_grad_prep(grad_y, y | None, relu)            -> (grad_y * (y > 0), its per-channel sums db)
+    conv3_wgrad(x, x2 | None, g, dtype)                -> dW (Co, Ci, 3, 3, 3)  f32
 """
 from __future__ import annotations
 
@@ -505,6 +508,84 @@ def conv3(src0: torch.Tensor, src1, packed: torch.Tensor, dst: torch.Tensor, dst
                           int(dst.shape[1]), int(dst_offset), int(cout), int(bool(relu)), B, H, W, D, dtype,
                           _stream(src0)), "conv3")
     return dst
+
+
+@_on_device
+def conv3_pack_dgrad(weight: torch.Tensor, dtype: int) -> torch.Tensor:
+    """A (cout, cin, 3, 3, 3) weight -> the packed operands of its input gradient (dvc_conv3_pack_dgrad): the layer
+    W'[ci][o][t'] = W[o][ci][26 - t'] with zero biases, so conv3(g, None, packed, dx, 0, cin, False, dtype) is
+    d loss / d cat[x, x2]."""
+    _need_cuda(weight)
+    if weight.ndim != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
+        raise ValueError(f"conv3_pack_dgrad: weight {tuple(weight.shape)} is not a 3 x 3 x 3 convolution's")
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    nbytes = lib().dvc_conv3_packed_bytes(cout, cin, dtype)
+    if nbytes == 0:
+        raise NotImplementedError(f"conv3_pack_dgrad: cin={cin} cout={cout} is outside the kernel's shapes "
+                                  f"(cin 1..{_lib.CONV3_MAX_CIN}, cout 1..{_lib.CONV3_MAX_COUT})")
+    w = _f32c(weight.detach())
+    out = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
+    check(lib().dvc_conv3_pack_dgrad(_ptr(w), _ptr(out), cin, cout, dtype, _stream(w)), "conv3_pack_dgrad")
+    return out
+
+
+@_on_device
+def conv3_grad_prep(grad_y: torch.Tensor, y, relu: bool):
+    """(g, db) of a layer's output gradient (dvc_conv3_grad_prep): g = grad_y * (y > 0) with ReLU (y the layer's own
+    output), else grad_y itself (no copy); db[o] = sum over (b, v) of g[b, o, v], summed in a fixed order."""
+    _need_cuda(grad_y)
+    _conv_operand(grad_y, "conv3_grad_prep: grad_y")
+    if grad_y.ndim != 5:
+        raise ValueError(f"conv3_grad_prep: grad_y must be (B, C, H, W, D), got {tuple(grad_y.shape)}")
+    g = None
+    if relu:
+        _need_cuda(y)
+        _conv_operand(y, "conv3_grad_prep: y")
+        if y.shape != grad_y.shape:
+            raise ValueError(f"conv3_grad_prep: y {tuple(y.shape)} does not match grad_y {tuple(grad_y.shape)}")
+        g = torch.empty_like(grad_y)
+    B, cout, H, W, D = grad_y.shape
+    nchunk = -(-(H * W * D) // _lib.CONV3_PREP_CHUNK)
+    db = torch.empty(cout, dtype=torch.float32, device=grad_y.device)
+    partial = torch.empty(cout * B * nchunk, dtype=torch.float32, device=grad_y.device)
+    check(lib().dvc_conv3_grad_prep(_ptr(grad_y), _ptr(y) if relu else None, _ptr(g) if relu else None, _ptr(db),
+                                    _ptr(partial), cout, B, H, W, D, _stream(grad_y)), "conv3_grad_prep")
+    return (g if relu else grad_y), db
+
+
+def conv3_wgrad_slabs(cin: int, cout: int, B: int, H: int, W: int, D: int):
+    """(K-blocks, K-blocks per slab, slabs) of dvc_conv3_wgrad's split-K (include/dvccorr.h): the K-blocks are the
+    CONV3_WGRAD_KH x KW x KD voxel boxes of the (B, H, W, D) grid in that order, D fastest."""
+    nbox = B * -(-H // _lib.CONV3_WGRAD_KH) * -(-W // _lib.CONV3_WGRAD_KW) * -(-D // _lib.CONV3_WGRAD_KD)
+    groups = 1 if cout <= 16 else -(-cout // 32)
+    want = min(nbox, -(-_lib.CONV3_WGRAD_TARGET // (-(-cin // 16) * groups)))
+    per = -(-nbox // want)
+    return nbox, per, -(-nbox // per)
+
+
+@_on_device
+def conv3_wgrad(x: torch.Tensor, x2, g: torch.Tensor, dtype: int) -> torch.Tensor:
+    """dW (cout, cin, 3, 3, 3) float32 of a 3 x 3 x 3 layer from its input cat[x, x2] (x2 may be None) and its masked
+    output gradient g (dvc_conv3_wgrad).  All tensors contiguous float32 (B, C, H, W, D)."""
+    ts = [x, g] + ([] if x2 is None else [x2])
+    _need_cuda(*ts)
+    for t in ts:
+        _conv_operand(t, "conv3_wgrad: x, x2 and g")
+        if t.ndim != 5 or t.shape[0] != x.shape[0] or t.shape[2:] != x.shape[2:]:
+            raise ValueError(f"conv3_wgrad: x, x2 and g must be (B, C, H, W, D) of one batch and volume; got "
+                             f"{[tuple(v.shape) for v in ts]}")
+    B, c0, H, W, D = x.shape
+    c1 = 0 if x2 is None else int(x2.shape[1])
+    cout = int(g.shape[1])
+    nws = lib().dvc_conv3_wgrad_workspace_bytes(c0 + c1, cout, B, H, W, D)
+    if nws == 0:
+        raise NotImplementedError(f"conv3_wgrad: cin={c0 + c1} cout={cout} is outside the kernel's shapes "
+                                  f"(cin 1..{_lib.CONV3_MAX_CIN}, cout 1..{_lib.CONV3_MAX_COUT})")
+    dw = torch.empty((cout, c0 + c1, 3, 3, 3), dtype=torch.float32, device=x.device)
+    ws = torch.empty(nws // 4, dtype=torch.float32, device=x.device)
+    check(lib().dvc_conv3_wgrad(_ptr(x), c0, None if x2 is None else _ptr(x2), c1, _ptr(g), cout, _ptr(dw), _ptr(ws),
+                                B, H, W, D, dtype, _stream(x)), "conv3_wgrad")
+    return dw
 
 
 @_on_device

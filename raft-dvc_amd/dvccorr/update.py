@@ -25,7 +25,8 @@ torch.cat per iteration:
     cor = corr_fn.lookup_convc1(coords1, convc1.weight, convc1.bias)
     net, delta_flow, log_b = block(net, context, flow, cor=cor)  # raft_dvc.py:468
 
-conv3x3x3 is the functional form of one such layer.
+conv3x3x3 is the functional form of one such layer, forward only; conv3x3x3_ad is the same layer with a backward
+(input, weight and bias gradients on csrc/conv3_grad.hip) for training.
 """
 from __future__ import annotations
 
@@ -37,7 +38,7 @@ import torch.nn.functional as F
 from . import _lib, ops
 from .corr_block import _wants_grad, resolve_precision
 
-__all__ = ["SepConvGRU", "sep_conv_gru", "GRU_WEIGHT_NAMES", "UpdateBlock", "conv3x3x3"]
+__all__ = ["SepConvGRU", "sep_conv_gru", "GRU_WEIGHT_NAMES", "UpdateBlock", "conv3x3x3", "conv3x3x3_ad"]
 
 _AXES = (("h", (2, 0, 0)), ("w", (0, 2, 0)), ("d", (0, 0, 2)))
 GRU_WEIGHT_NAMES = tuple(f"conv{g}_{ax}.{kind}" for ax, _ in _AXES for g in "zrq" for kind in ("weight", "bias"))
@@ -226,6 +227,33 @@ def conv3x3x3(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, *, relu
     x2 = None if x2 is None else ops._f32c(x2.detach())
     _conv3_layer(None, None, dtype, x, x2, weight, bias, out, out_offset, relu)
     return out
+
+
+def conv3x3x3_ad(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, *, relu: bool = False,
+                 precision: Optional[str] = None, x2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv3x3x3 as a differentiable function: F.conv3d(cat[x, x2], weight, bias, padding=1) (+ ReLU) on the matrix
+    cores, float32 out (a new tensor), with gradients for x, x2, weight and bias (dvccorr::conv3_ad).  The backward
+    runs k_conv3_grad_prep (ReLU mask from the op's own output, bias gradient), k_conv3_wgrad (weight gradient) and
+    k_conv3_mfma on the transposed, flipped weights (input gradient), skipping what no input asks for.  Precision as
+    conv3x3x3, in both directions: "fp16" / "bf16" round both operands of every product once and accumulate in fp32,
+    "fp32" splits them into bf16 hi + lo pieces.  Under "fp16" the incoming gradient is an operand and is rounded to
+    fp16 too, as the reference's AMP backward does: scale the loss (GradScaler) so that it stays in fp16's range.
+    The packed weights are cached per weight object until it changes (an optimiser step re-packs).  No double
+    backward.  Channel counts outside the kernel's (cin, cout <= 128) run F.conv3d in float32 with autograd on."""
+    srcs = (("x", x),) + ((("x2", x2),) if x2 is not None else ())
+    _same_volume("conv3x3x3", *srcs)
+    cin = x.shape[1] + (0 if x2 is None else x2.shape[1])
+    if weight.ndim != 5 or tuple(weight.shape[1:]) != (cin, 3, 3, 3) or tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError(f"conv3x3x3: weight {tuple(weight.shape)} bias {tuple(bias.shape)} do not match {cin} input "
+                         "channels of a 3 x 3 x 3 convolution")
+    ops._need_cuda(*(t for _, t in srcs), weight, bias)
+    if not conv_covers(cin, int(weight.shape[0])):
+        with torch.autocast("cuda", enabled=False):
+            xs = x.float() if x2 is None else torch.cat([x.float(), x2.float()], dim=1)
+            y = F.conv3d(xs, weight.float(), bias.float(), padding=1)
+            return F.relu(y) if relu else y
+    dtype = ops.dtype_code(resolve_precision(x, precision))
+    return torch.ops.dvccorr.conv3_ad(x, x2, weight, bias, bool(relu), dtype)
 
 
 class UpdateBlock:
