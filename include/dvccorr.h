@@ -377,6 +377,54 @@ size_t dvc_conv3_wgrad_workspace_bytes(int cin, int cout, int B, int H, int W, i
 int dvc_conv3_wgrad(const float *src0, int c0, const float *src1, int c1, const float *g, int cout, float *dw,
                     void *workspace, int B, int H, int W, int D, int dtype, void *stream);
 
+/* The backward of dvc_sep_gru_pass (csrc/gru_grad.hip).  All tensors (B, C, H, W, D) float32, contiguous; hidden is
+ * DVC_GRU_HIDDEN, input 1..DVC_GRU_MAX_INPUT.  With G = dL/dh_out of one axis pass:
+ *   dvc_sep_gru_pass_save   dvc_sep_gru_pass that also stores the pass's z, r and q (after tanh) into save, three
+ *               (B, hidden, H, W, D) tensors in a row.  h_out is bit-identical to dvc_sep_gru_pass's.  A GRU call keeps
+ *               z, r, q of its three passes and two intermediate hidden states: 11 * hidden * B H W D floats (138 MB at
+ *               32^3).
+ *   dvc_gru_pack_dgrad      the weights of the input gradient, W'[ci][o][t'] = w[o][ci][4 - t'] of (wq) and of (wz; wr),
+ *               dvc_gru_dgrad_packed_bytes bytes; used with the dtype it was packed for.
+ *   dvc_gru_grad_prep       a_q = G z (1 - q^2), a_z = G (q - h) z (1 - z), dh = G (1 - z), db_q and db_z (the sums of
+ *               a_q and a_z over (b, v), in a fixed order).  partial is a work buffer of 2 * hidden * B *
+ *               ceil(H W D / DVC_CONV3_PREP_CHUNK) floats.
+ *   dvc_sep_gru_dgrad       with D = wq^T *T a_q and E = (wz; wr)^T *T (a_z; a_r), *T the transposed 5-tap convolution
+ *               along the axis: writes a_r = D[:hidden] h r (1 - r), adds D[:hidden] r + E[:hidden] to dh (as left by
+ *               dvc_gru_grad_prep: dh is then dL/dh of the pass) and D[hidden:] + E[hidden:] to dx (dx_add != 0) or
+ *               stores it (dx_add == 0); dx may be NULL (no input gradient).  db_r is the sum of a_r; partial is
+ *               hidden * B * ceil(H W D / DVC_CONV3_PREP_CHUNK) floats.
+ *   dvc_gru_wgrad           dw[gate z, r, q][o][ci][t] = sum over (b, v) of a_gate[b, o, v] in_gate[b, ci, v + (t - 2) e],
+ *               in_z = in_r = cat[h, x], in_q = cat[r h, x]: the three (hidden, hidden + input, 5) weight gradients in
+ *               a row, as a GEMM over the voxels on the matrix cores.  A K-block is DVC_GRU_WGRAD_LINES lines x
+ *               DVC_GRU_WGRAD_POS positions; the nkb = ceil(lines / LINES) * ceil(len / POS) blocks are cut into slabs
+ *               of per = ceil(nkb / min(nkb, ceil(DVC_GRU_WGRAD_TARGET / (3 * ceil((hidden + input) / 16)))))
+ *               consecutive blocks; each of the ceil(nkb / per) slabs writes its partial to the workspace
+ *               (dvc_gru_wgrad_workspace_bytes = slabs * 3 * hidden * (hidden + input) * 5 * 4) and the slabs are summed
+ *               in index order (no slab is empty; bit-identical from run to run).
+ * dtype as the forward; for DVC_F16 the gradient operands are rounded to fp16 too (scale the loss as under AMP).
+ * No atomics, no allocation, no host synchronisation.  Errors as dvc_conv3_wgrad: a null pointer (dx excepted),
+ * B / H / W / D < 1, axis outside 0..2, a bad dtype or an output or workspace overlapping another buffer are
+ * DVC_ERR_INVALID; hidden != DVC_GRU_HIDDEN, input outside 1..DVC_GRU_MAX_INPUT or 2^31 voxels or more are
+ * DVC_ERR_UNSUPPORTED (the _bytes functions return 0). */
+#define DVC_GRU_WGRAD_LINES 32
+#define DVC_GRU_WGRAD_POS 4
+#define DVC_GRU_WGRAD_TARGET 512
+int dvc_sep_gru_pass_save(const float *h, const float *x, const void *packed, float *h_out, float *save, int B,
+                          int hidden, int input, int H, int W, int D, int axis, int dtype, void *stream);
+size_t dvc_gru_dgrad_packed_bytes(int hidden, int input, int dtype);
+int dvc_gru_pack_dgrad(const float *wz, const float *wr, const float *wq, void *packed, int hidden, int input,
+                       int dtype, void *stream);
+int dvc_gru_grad_prep(const float *g, const float *z, const float *q, const float *h, float *a_q, float *a_z,
+                      float *dh, float *db_q, float *db_z, float *partial, int B, int hidden, int H, int W, int D,
+                      void *stream);
+int dvc_sep_gru_dgrad(const float *a_q, const float *a_z, const float *h, const float *r, const void *packed,
+                      float *a_r, float *dh, float *dx_or_null, float *db_r, float *partial, int B, int hidden,
+                      int input, int H, int W, int D, int axis, int dx_add, int dtype, void *stream);
+size_t dvc_gru_wgrad_workspace_bytes(int hidden, int input, int B, int H, int W, int D, int axis);
+int dvc_gru_wgrad(const float *h, const float *x, const float *r, const float *a_z, const float *a_r,
+                  const float *a_q, float *dw, void *workspace, int B, int hidden, int input, int H, int W, int D,
+                  int axis, int dtype, void *stream);
+
 /* Diagnostics hook for A/B timing.  The product kernel selection is a fixed table;
  * an override set here is PROCESS-GLOBAL (round 6; it was thread-local, which a
  * backward run on the autograd engine's worker thread never saw): it changes every

@@ -73,8 +73,21 @@ __global__ void k_upflow(const float *, const float *, float *, float *, long lo
 size_t gru_packed_bytes(int dtype);
 hipError_t launch_gru_pack(const float *wz, const float *wr, const float *wq, const float *bz, const float *br,
                            const float *bq, void *packed, int Cx, int dtype, hipStream_t s);
-hipError_t launch_sep_gru_pass(const float *h, const float *x, const void *packed, float *h_out, int B, int Cx, int H,
-                               int W, int D, int axis, int dtype, hipStream_t s);
+hipError_t launch_sep_gru_pass(const float *h, const float *x, const void *packed, float *h_out, float *save, int B,
+                               int Cx, int H, int W, int D, int axis, int dtype, hipStream_t s);
+size_t gru_dgrad_packed_bytes(int dtype);
+hipError_t launch_gru_pack_dgrad(const float *wz, const float *wr, const float *wq, void *packed, int Cx, int dtype,
+                                 hipStream_t s);
+hipError_t launch_gru_grad_prep(const float *g, const float *z, const float *q, const float *h, float *aq, float *az,
+                                float *dh, float *dbq, float *dbz, float *partial, int B, int H, int W, int D,
+                                hipStream_t s);
+hipError_t launch_sep_gru_dgrad(const float *aq, const float *az, const float *h, const float *r, const void *packed,
+                                float *ar, float *dh, float *dx, float *dbr, float *partial, int B, int Cx, int H, int W,
+                                int D, int axis, int dx_add, int dtype, hipStream_t s);
+size_t gru_wgrad_workspace_bytes(int Cx, int B, int H, int W, int D, int axis);
+hipError_t launch_gru_wgrad(const float *h, const float *x, const float *r, const float *az, const float *ar,
+                            const float *aq, float *dw, void *workspace, int B, int Cx, int H, int W, int D, int axis,
+                            int dtype, hipStream_t s);
 size_t conv3_packed_bytes(int cin, int cout, int dtype);
 hipError_t launch_conv3_pack(const float *w, const float *bias, void *packed, int cin, int cout, int dtype,
                              hipStream_t s);
@@ -1220,8 +1233,118 @@ int dvc_sep_gru_pass(const float *h, const float *x, const void *packed, float *
     const size_t hb = (size_t)vox * hidden * 4, xb = (size_t)vox * input * 4;
     if (overlaps(h_out, hb, h, hb) || overlaps(h_out, hb, x, xb))
         return fail(DVC_ERR_INVALID, "sep_gru_pass: h_out must not overlap h or x (a pass reads its neighbours)");
-    return launched("sep_gru_pass",
-                    launch_sep_gru_pass(h, x, packed, h_out, B, input, H, W, D, axis, dtype, (hipStream_t)stream));
+    return launched("sep_gru_pass", launch_sep_gru_pass(h, x, packed, h_out, nullptr, B, input, H, W, D, axis, dtype,
+                                                        (hipStream_t)stream));
+}
+
+// the backward of dvc_sep_gru_pass (gru_grad.hip)
+struct Span {
+    const void *p;
+    size_t n;
+};
+
+// no output overlaps an input or another output
+static bool any_overlap(const Span *outs, int nout, const Span *ins, int nin) {
+    for (int i = 0; i < nout; ++i) {
+        if (!outs[i].p) continue;
+        for (int j = 0; j < nin; ++j)
+            if (ins[j].p && overlaps(outs[i].p, outs[i].n, ins[j].p, ins[j].n)) return true;
+        for (int j = i + 1; j < nout; ++j)
+            if (outs[j].p && overlaps(outs[i].p, outs[i].n, outs[j].p, outs[j].n)) return true;
+    }
+    return false;
+}
+
+static size_t prep_partial_bytes(int channels, int B, int H, int W, int D) {
+    return (size_t)channels * B * (size_t)ceil_div((long long)H * W * D, DVC_CONV3_PREP_CHUNK) * 4;
+}
+
+int dvc_sep_gru_pass_save(const float *h, const float *x, const void *packed, float *h_out, float *save, int B,
+                          int hidden, int input, int H, int W, int D, int axis, int dtype, void *stream) {
+    if (!h || !x || !packed || !h_out || !save) return fail(DVC_ERR_INVALID, "sep_gru_pass_save: null pointer");
+    if (int rc = volume_check("sep_gru_pass_save", B, H, W, D, "line indices")) return rc;
+    if (axis < 0 || axis > 2)
+        return fail(DVC_ERR_INVALID, "sep_gru_pass_save: axis %d is not 0 (h), 1 (w) or 2 (d)", axis);
+    if (int rc = gru_shape_check("sep_gru_pass_save", hidden, input, dtype)) return rc;
+    const size_t vox = (size_t)B * H * W * D * 4, hb = vox * hidden;
+    const Span outs[2] = {{h_out, hb}, {save, 3 * hb}};
+    const Span ins[3] = {{h, hb}, {x, vox * input}, {packed, gru_packed_bytes(dtype)}};
+    if (any_overlap(outs, 2, ins, 3))
+        return fail(DVC_ERR_INVALID, "sep_gru_pass_save: h_out and save must not overlap an input or each other");
+    return launched("sep_gru_pass_save", launch_sep_gru_pass(h, x, packed, h_out, save, B, input, H, W, D, axis, dtype,
+                                                             (hipStream_t)stream));
+}
+
+size_t dvc_gru_dgrad_packed_bytes(int hidden, int input, int dtype) {
+    if (gru_shape_check("gru_dgrad_packed_bytes", hidden, input, dtype)) return 0;
+    return gru_dgrad_packed_bytes(dtype);
+}
+
+int dvc_gru_pack_dgrad(const float *wz, const float *wr, const float *wq, void *packed, int hidden, int input,
+                       int dtype, void *stream) {
+    if (!wz || !wr || !wq || !packed) return fail(DVC_ERR_INVALID, "gru_pack_dgrad: null pointer");
+    if (int rc = gru_shape_check("gru_pack_dgrad", hidden, input, dtype)) return rc;
+    return launched("gru_pack_dgrad", launch_gru_pack_dgrad(wz, wr, wq, packed, input, dtype, (hipStream_t)stream));
+}
+
+int dvc_gru_grad_prep(const float *g, const float *z, const float *q, const float *h, float *a_q, float *a_z,
+                      float *dh, float *db_q, float *db_z, float *partial, int B, int hidden, int H, int W, int D,
+                      void *stream) {
+    if (!g || !z || !q || !h || !a_q || !a_z || !dh || !db_q || !db_z || !partial)
+        return fail(DVC_ERR_INVALID, "gru_grad_prep: null pointer");
+    if (int rc = volume_check("gru_grad_prep", B, H, W, D)) return rc;
+    if (int rc = gru_shape_check("gru_grad_prep", hidden, 1, DVC_F32)) return rc;
+    const size_t hb = (size_t)B * H * W * D * 4 * hidden;
+    const Span outs[6] = {{a_q, hb}, {a_z, hb}, {dh, hb}, {db_q, (size_t)hidden * 4}, {db_z, (size_t)hidden * 4},
+                          {partial, prep_partial_bytes(2 * hidden, B, H, W, D)}};
+    const Span ins[4] = {{g, hb}, {z, hb}, {q, hb}, {h, hb}};
+    if (any_overlap(outs, 6, ins, 4))
+        return fail(DVC_ERR_INVALID, "gru_grad_prep: an output must not overlap an input or another output");
+    return launched("gru_grad_prep",
+                    launch_gru_grad_prep(g, z, q, h, a_q, a_z, dh, db_q, db_z, partial, B, H, W, D, (hipStream_t)stream));
+}
+
+int dvc_sep_gru_dgrad(const float *a_q, const float *a_z, const float *h, const float *r, const void *packed,
+                      float *a_r, float *dh, float *dx_or_null, float *db_r, float *partial, int B, int hidden,
+                      int input, int H, int W, int D, int axis, int dx_add, int dtype, void *stream) {
+    if (!a_q || !a_z || !h || !r || !packed || !a_r || !dh || !db_r || !partial)
+        return fail(DVC_ERR_INVALID, "sep_gru_dgrad: null pointer");
+    if (int rc = volume_check("sep_gru_dgrad", B, H, W, D, "line indices")) return rc;
+    if (axis < 0 || axis > 2) return fail(DVC_ERR_INVALID, "sep_gru_dgrad: axis %d is not 0 (h), 1 (w) or 2 (d)", axis);
+    if (int rc = gru_shape_check("sep_gru_dgrad", hidden, input, dtype)) return rc;
+    const size_t vox = (size_t)B * H * W * D * 4, hb = vox * hidden;
+    const Span outs[5] = {{a_r, hb}, {dh, hb}, {dx_or_null, vox * input}, {db_r, (size_t)hidden * 4},
+                          {partial, prep_partial_bytes(hidden, B, H, W, D)}};
+    const Span ins[5] = {{a_q, hb}, {a_z, hb}, {h, hb}, {r, hb}, {packed, gru_dgrad_packed_bytes(dtype)}};
+    if (any_overlap(outs, 5, ins, 5))
+        return fail(DVC_ERR_INVALID, "sep_gru_dgrad: an output must not overlap an input or another output");
+    return launched("sep_gru_dgrad", launch_sep_gru_dgrad(a_q, a_z, h, r, packed, a_r, dh, dx_or_null, db_r, partial, B,
+                                                          input, H, W, D, axis, dx_add != 0, dtype, (hipStream_t)stream));
+}
+
+size_t dvc_gru_wgrad_workspace_bytes(int hidden, int input, int B, int H, int W, int D, int axis) {
+    if (gru_shape_check("gru_wgrad_workspace_bytes", hidden, input, DVC_F32)) return 0;
+    if (volume_check("gru_wgrad_workspace_bytes", B, H, W, D)) return 0;
+    if (axis < 0 || axis > 2) return 0;
+    return gru_wgrad_workspace_bytes(input, B, H, W, D, axis);
+}
+
+int dvc_gru_wgrad(const float *h, const float *x, const float *r, const float *a_z, const float *a_r,
+                  const float *a_q, float *dw, void *workspace, int B, int hidden, int input, int H, int W, int D,
+                  int axis, int dtype, void *stream) {
+    if (!h || !x || !r || !a_z || !a_r || !a_q || !dw || !workspace)
+        return fail(DVC_ERR_INVALID, "gru_wgrad: null pointer");
+    if (int rc = volume_check("gru_wgrad", B, H, W, D, "line indices")) return rc;
+    if (axis < 0 || axis > 2) return fail(DVC_ERR_INVALID, "gru_wgrad: axis %d is not 0 (h), 1 (w) or 2 (d)", axis);
+    if (int rc = gru_shape_check("gru_wgrad", hidden, input, dtype)) return rc;
+    const size_t vox = (size_t)B * H * W * D * 4, hb = vox * hidden;
+    const Span outs[2] = {{dw, (size_t)3 * hidden * (hidden + input) * 5 * 4},
+                          {workspace, gru_wgrad_workspace_bytes(input, B, H, W, D, axis)}};
+    const Span ins[6] = {{h, hb}, {x, vox * input}, {r, hb}, {a_z, hb}, {a_r, hb}, {a_q, hb}};
+    if (any_overlap(outs, 2, ins, 6))
+        return fail(DVC_ERR_INVALID, "gru_wgrad: dw and the workspace must not overlap an input or each other");
+    return launched("gru_wgrad", launch_gru_wgrad(h, x, r, a_z, a_r, a_q, dw, workspace, B, input, H, W, D, axis, dtype,
+                                                  (hipStream_t)stream));
 }
 
 // the update block's plain convolutions (conv3.hip): the shapes k_conv3_mfma covers

@@ -246,6 +246,12 @@ __global__ __launch_bounds__(256) void k_conv3_wgrad_reduce(const float *__restr
     dw[e] = s;
 }
 
+// the split-K reduce on its own: k_gru_wgrad (gru_grad.hip) shares it
+hipError_t launch_wgrad_reduce(const float *ws, float *dw, int n, int nslab, hipStream_t s) {
+    k_conv3_wgrad_reduce<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(ws, dw, n, nslab);
+    return hipGetLastError();
+}
+
 // host entry: arguments validated by dvc_conv3_wgrad (capi.hip)
 hipError_t launch_conv3_wgrad(const float *src0, int c0, const float *src1, int c1, const float *g, int cout, float *dw,
                               void *workspace, int B, int H, int W, int D, int dtype, hipStream_t s) {
@@ -264,9 +270,7 @@ hipError_t launch_conv3_wgrad(const float *src0, int c0, const float *src1, int 
     });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const int n = cout * cin * 27;
-    k_conv3_wgrad_reduce<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(A.ws, dw, n, A.nslab);
-    return hipGetLastError();
+    return launch_wgrad_reduce(A.ws, dw, cout * cin * 27, A.nslab, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

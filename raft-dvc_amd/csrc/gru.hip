@@ -47,24 +47,14 @@ struct GruArgs {
     const float *h, *x;
     const unsigned char *w;   // packed weights of this axis (dvc_gru_pack), then 288 fp32 biases (z, r, q)
     float *out;
+    float *save;              // SAVE: z, r, q (after tanh) of the centre positions, three (B, 96, H, W, D) tensors in a row
     long long HWD, pstride;   // channel stride; stride of one step along the conv axis
     int B, Cx, H, W, D, axis, len, nlines, per_b;
 };
 
-// line n of the pass -> batch element and spatial offset of its position 0
-__device__ __forceinline__ bool gru_line(const GruArgs &A, int n, int &b, long long &off) {
-    b = 0;
-    off = 0;
-    if (n >= A.nlines) return false;
-    b = n / A.per_b;
-    const int r = n - b * A.per_b;
-    off = A.axis == 0 ? (long long)r : A.axis == 1 ? (long long)(r / A.D) * A.W * A.D + r % A.D : (long long)r * A.D;
-    return true;
-}
-
 __device__ __forceinline__ float gru_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
-template <typename T, int NP>
+template <typename T, int NP, bool SAVE>
 __global__ __launch_bounds__(256, 1) void k_sep_gru_pass(GruArgs A) {
     constexpr int S = GRU_S, PB = (S + 4) / 4, ROWB = kRowBytes, PIECE = 16 * (S + 8) * ROWB;
     static_assert(S == 8, "256 threads stage (S + 8) positions x 16 lines, one voxel each");
@@ -94,6 +84,8 @@ __global__ __launch_bounds__(256, 1) void k_sep_gru_pass(GruArgs A) {
     const bool mok = gru_line(A, lg * 16 + m16, mb, moff);
     const float *mh = A.h + (long long)mb * GRU_HID * HWD + moff;
     float *mo = A.out + (long long)mb * GRU_HID * HWD + moff;
+    float *ms = SAVE ? A.save + (long long)mb * GRU_HID * HWD + moff : nullptr;
+    const long long NS = (long long)A.B * GRU_HID * HWD;   // one saved tensor
 
     const unsigned char *w1 = A.w + lane * 16;
     const unsigned char *w2 = w1 + (long long)GRU_UNITS1 * 6 * NP * kFragBytes;
@@ -184,6 +176,17 @@ __global__ __launch_bounds__(256, 1) void k_sep_gru_pass(GruArgs A) {
         pv[i] = q >= 0 && q < S;
         ppos[i] = seg0 + q;
     }
+    if constexpr (SAVE) {   // r leaves now: its registers are free after the last r h chunk
+#pragma unroll
+        for (int i = 0; i < PB; ++i) {
+            if (!(pv[i] && mok && ppos[i] < A.len)) continue;
+#pragma unroll
+            for (int t = 0; t < 6; ++t)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    ms[NS + (long long)(16 * t + 4 * h4 + k) * HWD + (long long)ppos[i] * A.pstride] = rg[t][i][k];
+        }
+    }
     f32x4 acq[6][PB];
 #pragma unroll
     for (int t = 0; t < 6; ++t)
@@ -256,6 +259,10 @@ __global__ __launch_bounds__(256, 1) void k_sep_gru_pass(GruArgs A) {
                 const float q = tanhf(acq[t][i][k] + bias[2 * GRU_HID + o0 + k]);
                 const float z = zg[t][i][k];
                 mo[base + (long long)k * HWD] = (1.0f - z) * hv + z * q;
+                if constexpr (SAVE) {
+                    ms[base + (long long)k * HWD] = z;
+                    ms[2 * NS + base + (long long)k * HWD] = q;
+                }
             }
         }
     }
@@ -310,11 +317,11 @@ hipError_t launch_gru_pack(const float *wz, const float *wr, const float *wq, co
     return hipGetLastError();
 }
 
-// host entry: arguments validated by dvc_sep_gru_pass (capi.hip)
-hipError_t launch_sep_gru_pass(const float *h, const float *x, const void *packed, float *h_out, int B, int Cx, int H,
-                               int W, int D, int axis, int dtype, hipStream_t s) {
+// host entry: arguments validated by dvc_sep_gru_pass / dvc_sep_gru_pass_save (capi.hip); save = nullptr: inference
+hipError_t launch_sep_gru_pass(const float *h, const float *x, const void *packed, float *h_out, float *save, int B,
+                               int Cx, int H, int W, int D, int axis, int dtype, hipStream_t s) {
     GruArgs A;
-    A.h = h; A.x = x; A.w = static_cast<const unsigned char *>(packed); A.out = h_out;
+    A.h = h; A.x = x; A.w = static_cast<const unsigned char *>(packed); A.out = h_out; A.save = save;
     A.B = B; A.Cx = Cx; A.H = H; A.W = W; A.D = D; A.axis = axis;
     A.HWD = (long long)H * W * D;
     A.len = axis == 0 ? H : axis == 1 ? W : D;
@@ -323,7 +330,8 @@ hipError_t launch_sep_gru_pass(const float *h, const float *x, const void *packe
     A.nlines = B * A.per_b;
     const unsigned grid = (unsigned)((A.nlines + 15) / 16) * (unsigned)((A.len + GRU_S - 1) / GRU_S);
     with_precision(dtype, [&](auto t, auto np) {
-        k_sep_gru_pass<decltype(t), decltype(np)::value><<<grid, 256, 0, s>>>(A);
+        if (save) k_sep_gru_pass<decltype(t), decltype(np)::value, true><<<grid, 256, 0, s>>>(A);
+        else k_sep_gru_pass<decltype(t), decltype(np)::value, false><<<grid, 256, 0, s>>>(A);
     });
     return hipGetLastError();
 }

@@ -128,4 +128,16 @@ __device__ __forceinline__ void box_of_block(unsigned bid, int nth, int ntw, int
     b = (int)(bid / (unsigned)nth);
 }
 
+// Line n of a GRU axis pass (a line = the voxels that differ only in the conv-axis coordinate) -> batch element and
+// spatial offset of its position 0.  A has nlines, per_b (lines per batch element), axis, W and D.
+template <typename Args> __device__ __forceinline__ bool gru_line(const Args &A, int n, int &b, long long &off) {
+    b = 0;
+    off = 0;
+    if (n >= A.nlines) return false;
+    b = n / A.per_b;
+    const int r = n - b * A.per_b;
+    off = A.axis == 0 ? (long long)r : A.axis == 1 ? (long long)(r / A.D) * A.W * A.D + r % A.D : (long long)r * A.D;
+    return true;
+}
+
 }  // namespace dvc

@@ -34,6 +34,8 @@ EXPORTED = (
     "dvc_conv3_packed_bytes", "dvc_conv3_pack", "dvc_conv3",
     "dvc_conv7_flow_packed_bytes", "dvc_conv7_flow_pack", "dvc_conv7_flow",
     "dvc_conv3_pack_dgrad", "dvc_conv3_grad_prep", "dvc_conv3_wgrad_workspace_bytes", "dvc_conv3_wgrad",
+    "dvc_sep_gru_pass_save", "dvc_gru_dgrad_packed_bytes", "dvc_gru_pack_dgrad", "dvc_gru_grad_prep",
+    "dvc_sep_gru_dgrad", "dvc_gru_wgrad_workspace_bytes", "dvc_gru_wgrad",
 )
 PROJ_COUT = 96          # DVC_PROJ_COUT (convc1 output channels, update.py:222)
 PROJ_MAX_RADIUS = 4     # DVC_PROJ_MAX_RADIUS
@@ -48,6 +50,9 @@ CONV3_MAX_COUT = 128    # DVC_CONV3_MAX_COUT
 CONV3_WGRAD_KH, CONV3_WGRAD_KW, CONV3_WGRAD_KD = 4, 4, 16
 CONV3_WGRAD_TARGET = 512
 CONV3_PREP_CHUNK = 4096
+# DVC_GRU_WGRAD_LINES x DVC_GRU_WGRAD_POS: the K-block of k_gru_wgrad; DVC_GRU_WGRAD_TARGET: the workgroups its slab rule
+# aims for (ops.gru_wgrad_slabs)
+GRU_WGRAD_LINES, GRU_WGRAD_POS, GRU_WGRAD_TARGET = 32, 4, 512
 CONV7_TH, CONV7_TW, CONV7_TD = 4, 4, 16     # DVC_CONV7_TH / TW / TD: output box of one k_conv7_flow workgroup
 CONV7_COUT = 64         # DVC_CONV7_COUT (encoder.convf1, update.py:225)
 
@@ -128,6 +133,13 @@ def lib() -> ctypes.CDLL:
         "dvc_conv3_grad_prep": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
         "dvc_conv3_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
         "dvc_conv3_wgrad": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp]),
+        "dvc_sep_gru_pass_save": (i32, [vp] * 5 + [i32] * 8 + [vp]),
+        "dvc_gru_dgrad_packed_bytes": (sz, [i32, i32, i32]),
+        "dvc_gru_pack_dgrad": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+        "dvc_gru_grad_prep": (i32, [vp] * 10 + [i32] * 5 + [vp]),
+        "dvc_sep_gru_dgrad": (i32, [vp] * 10 + [i32] * 9 + [vp]),
+        "dvc_gru_wgrad_workspace_bytes": (sz, [i32] * 7),
+        "dvc_gru_wgrad": (i32, [vp] * 8 + [i32] * 8 + [vp]),
         "dvc_conv7_flow_packed_bytes": (sz, [i32]),
         "dvc_conv7_flow_pack": (i32, [vp, vp, vp, i32, vp]),
         "dvc_conv7_flow": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),

@@ -30,6 +30,14 @@ the PyTorch dispatcher as named operators with shape functions:
         g, dtype) -> dW and dvccorr::conv3 on g with the transposed, flipped weights of dvccorr::conv3_pack_dgrad(weight,
         dtype) (a cached pack, no compute)
 
+    dvccorr::sep_gru_ad(h, x, weights[18], dtype) -> (h_out, saved)   SepConvGRU3D.forward as a differentiable op
+        (update.py:167-199): the training forward keeps z, r, q of the three passes and the two intermediate hidden
+        states in `saved` (non-differentiable); its registered backward runs, per pass and in reverse,
+        dvccorr::gru_grad_prep(g, z, q, h) -> (a_q, a_z, dh0, db_q, db_z), dvccorr::gru_dgrad(a_q, a_z, h, r, packed, dh,
+        dx?, axis, dx_add, dtype) -> (a_r, db_r) (dh and dx updated in place) with the weights of
+        dvccorr::gru_pack_dgrad(weights, dtype) (a cached pack) and dvccorr::gru_wgrad(h, x, r, a_z, a_r, a_q, axis,
+        dtype) -> dW of the pass's three convolutions
+
 Every op runs the HIP kernels of libdvccorr.so through ops.py (no CPU
 fallback); the fake (meta) implementations only compute output shapes, so the
 ops trace under torch.compile / FakeTensorMode and torch.library.opcheck.
@@ -39,7 +47,7 @@ backward pass.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Sequence
 
 import torch
 from torch import Tensor
@@ -363,4 +371,128 @@ def _conv3_ad_backward(ctx, grad_y):
 torch.library.register_autograd("dvccorr::conv3_ad", _conv3_ad_backward, setup_context=_conv3_ad_setup)
 
 
-__all__ = ["conv3_ad", "conv3_grad_prep", "conv3_wgrad", "conv3_pack_dgrad", "sep_gru", "conv3", "conv7_flow", "build", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "lookup_ad", "lookup_convc1_ad"]
+# ---------------------------------------------------------------------------------------------------------------
+# a differentiable SepConvGRU3D (dvccorr.sep_conv_gru_ad): forward k_sep_gru_pass<SAVE>, backward csrc/gru_grad.hip
+# ---------------------------------------------------------------------------------------------------------------
+_GRU_NAMES = tuple(f"conv{g}_{ax}.{kind}" for ax in "hwd" for g in "zrq" for kind in ("weight", "bias"))
+
+
+def _gru_dict(weights):
+    if len(weights) != len(_GRU_NAMES):
+        raise ValueError(f"sep_gru_ad: {len(weights)} weight tensors; SepConvGRU3D has {len(_GRU_NAMES)} "
+                         "(update.GRU_WEIGHT_NAMES order)")
+    return dict(zip(_GRU_NAMES, weights))
+
+
+def _gru_packed(weights, dtype: int, kind: str, pack) -> Tensor:
+    if len(_conv3_packs()._entries) > _CONV3_AD_MAX_PACKS:
+        _conv3_packs()._entries.clear()
+    return _conv3_packs().get((kind, id(weights[0]), dtype), weights, lambda: pack(_gru_dict(weights), dtype))
+
+
+@torch.library.custom_op("dvccorr::gru_pack_dgrad", mutates_args=())
+def gru_pack_dgrad(weights: Sequence[Tensor], dtype: int) -> Tensor:
+    """ops.gru_pack_dgrad through the pack cache (an optimiser step re-packs), as an operator so that the backward of
+    dvccorr::sep_gru_ad traces."""
+    return _gru_packed(list(weights), dtype, "gru_dgrad", ops.gru_pack_dgrad)
+
+
+@gru_pack_dgrad.register_fake
+def _(weights, dtype):
+    # 3 x dvc_gru_dgrad_packed_bytes: (3 + 6) chunks x 5 taps x 16 tiles of 1 KB fragments, two pieces for fp32
+    return weights[0].new_empty((3, 720 * (2 if dtype == ops.DVC_F32 else 1) * 256), dtype=_F32)
+
+
+@torch.library.custom_op("dvccorr::sep_gru_ad", mutates_args=())
+def sep_gru_ad(h: Tensor, x: Tensor, weights: Sequence[Tensor], dtype: int) -> tuple[Tensor, Tensor]:
+    """SepConvGRU3D.forward(h, x) as a differentiable op: (h_out, saved).  saved (11, B, 96, H, W, D) float32 holds z, r,
+    q of the three passes and the hidden states after the h and w passes for the backward: 11 x 96 x B H W D floats,
+    138 MB at 32^3.  h, x and the eighteen weights carry gradients; saved does not."""
+    packed = _gru_packed(list(weights), dtype, "gru_fwd", ops.gru_pack)
+    return ops.sep_gru_save(h, x, packed, dtype)
+
+
+@sep_gru_ad.register_fake
+def _(h, x, weights, dtype):
+    return h.new_empty(h.shape, dtype=_F32), h.new_empty((11,) + tuple(h.shape), dtype=_F32)
+
+
+@torch.library.custom_op("dvccorr::gru_grad_prep", mutates_args=())
+def gru_grad_prep(g: Tensor, z: Tensor, q: Tensor, h: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    return ops.gru_grad_prep(g, z, q, h)
+
+
+@gru_grad_prep.register_fake
+def _(g, z, q, h):
+    e, b = (lambda: g.new_empty(g.shape, dtype=_F32)), (lambda: g.new_empty((g.shape[1],), dtype=_F32))
+    return e(), e(), e(), b(), b()
+
+
+@torch.library.custom_op("dvccorr::gru_dgrad", mutates_args=("dh", "dx"))
+def gru_dgrad(aq: Tensor, az: Tensor, h: Tensor, r: Tensor, packed: Tensor, dh: Tensor, dx: Optional[Tensor],
+              axis: int, dx_add: bool, dtype: int) -> tuple[Tensor, Tensor]:
+    return ops.sep_gru_dgrad(aq, az, h, r, packed[axis], dh, dx, axis, dx_add, dtype)
+
+
+@gru_dgrad.register_fake
+def _(aq, az, h, r, packed, dh, dx, axis, dx_add, dtype):
+    return aq.new_empty(aq.shape, dtype=_F32), aq.new_empty((aq.shape[1],), dtype=_F32)
+
+
+@torch.library.custom_op("dvccorr::gru_wgrad", mutates_args=())
+def gru_wgrad(h: Tensor, x: Tensor, r: Tensor, az: Tensor, ar: Tensor, aq: Tensor, axis: int, dtype: int) -> Tensor:
+    return ops.gru_wgrad(h, x, r, az, ar, aq, axis, dtype)
+
+
+@gru_wgrad.register_fake
+def _(h, x, r, az, ar, aq, axis, dtype):
+    return h.new_empty((3, h.shape[1], h.shape[1] + x.shape[1], 5), dtype=_F32)
+
+
+def _sep_gru_ad_setup(ctx, inputs, output):
+    h, x, weights, dtype = inputs
+    _, saved = output
+    ctx.mark_non_differentiable(saved)
+    ctx.save_for_backward(h, x, saved, *weights)
+    ctx.dtype = int(dtype)
+
+
+def _sep_gru_ad_backward(ctx, grad_h, _grad_saved=None):
+    """The three passes in reverse (d, w, h): dh of one pass is the incoming gradient of the pass before it, dx is
+    the sum over the passes (the first pass to run stores, the others add).  k_gru_wgrad runs only for an axis with a
+    weight that asks, dx is accumulated only when x asks; the bias gradients come with the prep and dgrad kernels."""
+    if grad_h.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("dvccorr.sep_conv_gru_ad has no double backward")
+    h, x, saved, *weights = ctx.saved_tensors
+    need_h, need_x, need_ws = ctx.needs_input_grad[0], ctx.needs_input_grad[1], list(ctx.needs_input_grad[2])
+    grads = [None] * len(weights)
+    if not (need_h or need_x or any(need_ws)):
+        return None, None, grads, None
+    dtype = ctx.dtype
+    hf, xf = ops._f32c(h), ops._f32c(x)
+    packed = gru_pack_dgrad(weights, dtype)
+    g = ops._f32c(grad_h)
+    dx = torch.empty_like(xf) if need_x else None
+    for a in (2, 1, 0):
+        if a == 0 and not (need_h or need_x or any(need_ws[:6])):
+            break   # nothing upstream of the h pass asks
+        h_in = (hf, saved[9], saved[10])[a]
+        z, r, q = saved[3 * a], saved[3 * a + 1], saved[3 * a + 2]
+        aq, az, dh, dbq, dbz = gru_grad_prep(g, z, q, h_in)
+        ar, dbr = gru_dgrad(aq, az, h_in, r, packed, dh, dx, a, a != 2, dtype)
+        n = need_ws[6 * a:6 * a + 6]
+        if n[0] or n[2] or n[4]:
+            dw = gru_wgrad(h_in, xf, r, az, ar, aq, a, dtype)
+        for k, db in enumerate((dbz, dbr, dbq)):
+            if n[2 * k]:
+                grads[6 * a + 2 * k] = dw[k].reshape(weights[6 * a + 2 * k].shape).to(weights[6 * a + 2 * k].dtype)
+            if n[2 * k + 1]:
+                grads[6 * a + 2 * k + 1] = db.to(weights[6 * a + 2 * k + 1].dtype)
+        g = dh
+    return (g.to(h.dtype) if need_h else None), (dx.to(x.dtype) if need_x else None), grads, None
+
+
+torch.library.register_autograd("dvccorr::sep_gru_ad", _sep_gru_ad_backward, setup_context=_sep_gru_ad_setup)
+
+
+__all__ = ["sep_gru_ad", "gru_pack_dgrad", "gru_grad_prep", "gru_dgrad", "gru_wgrad", "conv3_ad", "conv3_grad_prep", "conv3_wgrad", "conv3_pack_dgrad", "sep_gru", "conv3", "conv7_flow", "build", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "lookup_ad", "lookup_convc1_ad"]

@@ -23,6 +23,11 @@ straight to libdvccorr.so (no CPU fallback).  Shapes follow include/dvccorr.h:
     conv3_pack_dgrad(weight, dtype)                    -> packed weights of the layer's input gradient (run by conv3)
     conv3_grad_prep(grad_y, y | None, relu)            -> (grad_y * (y > 0), its per-channel sums db)
     conv3_wgrad(x, x2 | None, g, dtype)                -> dW (Co, Ci, 3, 3, 3)  f32
+    sep_gru_save(h, x, packed, dtype)                  -> (h after the three passes, saved (11, B, 96, H, W, D))  f32
+    gru_pack_dgrad(18 SepConvGRU3D tensors, dtype)     -> packed weights of the three passes' input gradients
+    gru_grad_prep(g, z, q, h)                          -> (a_q, a_z, dh0, db_q, db_z) of one pass
+    sep_gru_dgrad(a_q, a_z, h, r, packed_axis, dh, dx | None, axis, dx_add, dtype) -> (a_r, db_r); dh, dx in place
+    gru_wgrad(h, x, r, a_z, a_r, a_q, axis, dtype)     -> dW (3, 96, 96 + Ci, 5) of one pass  f32
 """
 from __future__ import annotations
 
@@ -461,6 +466,138 @@ def sep_gru(h: torch.Tensor, x: torch.Tensor, packed: torch.Tensor, dtype: int) 
     sep_gru_pass(a, x, packed[1], b, 1, dtype)
     sep_gru_pass(b, x, packed[2], a, 2, dtype)
     return a
+
+
+def _gru_tensors(what: str, hidden_like, x=None) -> tuple:
+    """(B, hidden, H, W, D) of contiguous float32 (B, hidden, H, W, D) tensors of one volume (x: (B, input, ...))."""
+    ts = list(hidden_like) + ([] if x is None else [x])
+    _need_cuda(*ts)
+    for t in ts:
+        _conv_operand(t, f"{what}: tensors")
+        if t.ndim != 5 or t.shape[0] != ts[0].shape[0] or t.shape[2:] != ts[0].shape[2:]:
+            raise ValueError(f"{what}: tensors must be (B, C, H, W, D) of one batch and volume; got "
+                             f"{[tuple(v.shape) for v in ts]}")
+    for t in hidden_like:
+        if t.shape[1] != ts[0].shape[1]:
+            raise ValueError(f"{what}: hidden-state tensors differ in channels: {[tuple(v.shape) for v in hidden_like]}")
+    return tuple(ts[0].shape)
+
+
+@_on_device
+def sep_gru_pass_save(h: torch.Tensor, x: torch.Tensor, packed_axis: torch.Tensor, out: torch.Tensor,
+                      save: torch.Tensor, axis: int, dtype: int) -> torch.Tensor:
+    """One axis pass that also stores z, r, q (after tanh) into save (3, B, hidden, H, W, D) (dvc_sep_gru_pass_save);
+    all tensors contiguous float32, out and save overlapping nothing."""
+    B, hidden, H, W, D = _gru_tensors("sep_gru_pass_save", (h, out), x)
+    _need_cuda(packed_axis, save)
+    _conv_operand(save, "sep_gru_pass_save: save")
+    if tuple(save.shape) != (3,) + tuple(h.shape):
+        raise ValueError(f"sep_gru_pass_save: save {tuple(save.shape)} is not (3,) + h's {tuple(h.shape)}")
+    check(lib().dvc_sep_gru_pass_save(_ptr(h), _ptr(x), _ptr(packed_axis), _ptr(out), _ptr(save), B, hidden,
+                                      x.shape[1], H, W, D, axis, dtype, _stream(h)), "sep_gru_pass_save")
+    return out
+
+
+@_on_device
+def sep_gru_save(h: torch.Tensor, x: torch.Tensor, packed: torch.Tensor, dtype: int):
+    """sep_gru for training (dvc_sep_gru_pass_save): (h_out, saved).  saved is (11, B, hidden, H, W, D) float32: z, r, q
+    (after tanh) of the h pass, of the w pass and of the d pass, then the hidden states after the h and the w pass --
+    11 x 96 x B H W D floats, 138 MB at 32^3.  h_out is bit-identical to sep_gru's."""
+    _need_cuda(h, x, packed)
+    h, x = _f32c(h), _f32c(x)
+    need = 3 * lib().dvc_gru_packed_bytes(h.shape[1], x.shape[1], dtype)
+    _check_packed("sep_gru_save", packed, need, f"hidden {h.shape[1]}, input {x.shape[1]} and this precision take "
+                  f"{need} (gru_pack with the same dtype)")
+    saved = torch.empty((11,) + tuple(h.shape), dtype=torch.float32, device=h.device)
+    out = torch.empty_like(h)
+    src = h
+    for a, dst in enumerate((saved[9], saved[10], out)):
+        src = sep_gru_pass_save(src, x, packed[a], dst, saved[3 * a:3 * a + 3], a, dtype)
+    return out, saved
+
+
+@_on_device
+def gru_pack_dgrad(weights, dtype: int) -> torch.Tensor:
+    """The nine SepConvGRU3D weights -> the three axes' packed input-gradient operands (dvc_gru_pack_dgrad;
+    3 x dvc_gru_dgrad_packed_bytes): W'[ci][o][t'] = W[o][ci][4 - t'] of wq and of (wz; wr)."""
+    wz = weights["convz_h.weight"]
+    _need_cuda(wz)
+    hidden, cin = int(wz.shape[0]), int(wz.shape[1])
+    nbytes = lib().dvc_gru_dgrad_packed_bytes(hidden, cin - hidden, dtype)
+    if nbytes == 0:
+        raise NotImplementedError(f"gru_pack_dgrad: hidden={hidden} input={cin - hidden} is outside the kernel's shapes "
+                                  f"(hidden {_lib.GRU_HIDDEN}, input 1..{_lib.GRU_MAX_INPUT})")
+    out = torch.empty((3, nbytes // 4), dtype=torch.float32, device=wz.device)
+    for a, ax in enumerate(_GRU_AXES):
+        ws = [_f32c(weights[f"conv{g}_{ax}.weight"].detach().reshape(hidden, cin, 5)) for g in "zrq"]
+        check(lib().dvc_gru_pack_dgrad(*map(_ptr, ws), _ptr(out[a]), hidden, cin - hidden, dtype, _stream(wz)),
+              "gru_pack_dgrad")
+    return out
+
+
+def _prep_chunks(H: int, W: int, D: int) -> int:
+    return -(-(H * W * D) // _lib.CONV3_PREP_CHUNK)
+
+
+@_on_device
+def gru_grad_prep(g: torch.Tensor, z: torch.Tensor, q: torch.Tensor, h: torch.Tensor):
+    """(a_q, a_z, dh0, db_q, db_z) of one axis pass (dvc_gru_grad_prep): a_q = g z (1 - q^2), a_z = g (q - h) z (1 - z),
+    dh0 = g (1 - z) and the bias gradients of the q and z gates, summed in a fixed order."""
+    B, hidden, H, W, D = _gru_tensors("gru_grad_prep", (g, z, q, h))
+    aq, az, dh = torch.empty_like(g), torch.empty_like(g), torch.empty_like(g)
+    dbq, dbz = (torch.empty(hidden, dtype=torch.float32, device=g.device) for _ in range(2))
+    partial = torch.empty(2 * hidden * B * _prep_chunks(H, W, D), dtype=torch.float32, device=g.device)
+    check(lib().dvc_gru_grad_prep(*map(_ptr, (g, z, q, h, aq, az, dh, dbq, dbz, partial)), B, hidden, H, W, D,
+                                  _stream(g)), "gru_grad_prep")
+    return aq, az, dh, dbq, dbz
+
+
+@_on_device
+def sep_gru_dgrad(aq: torch.Tensor, az: torch.Tensor, h: torch.Tensor, r: torch.Tensor, packed_axis: torch.Tensor,
+                  dh: torch.Tensor, dx, axis: int, dx_add: bool, dtype: int):
+    """The input gradient of one axis pass (dvc_sep_gru_dgrad): returns (a_r, db_r); dh (gru_grad_prep's dh0) becomes
+    dL/dh of the pass in place; dx (None: skipped) receives, or with dx_add accumulates, dL/dx of the pass."""
+    B, hidden, H, W, D = _gru_tensors("sep_gru_dgrad", (aq, az, h, r, dh), dx)
+    _need_cuda(packed_axis)
+    inp = 1 if dx is None else int(dx.shape[1])   # without dx the kernel computes the hidden tiles only
+    need = lib().dvc_gru_dgrad_packed_bytes(hidden, inp, dtype)
+    _check_packed("sep_gru_dgrad", packed_axis, need, f"hidden {hidden} and this precision take {need} "
+                  "(gru_pack_dgrad with the same dtype)")
+    ar = torch.empty_like(aq)
+    dbr = torch.empty(hidden, dtype=torch.float32, device=aq.device)
+    partial = torch.empty(hidden * B * _prep_chunks(H, W, D), dtype=torch.float32, device=aq.device)
+    check(lib().dvc_sep_gru_dgrad(_ptr(aq), _ptr(az), _ptr(h), _ptr(r), _ptr(packed_axis), _ptr(ar), _ptr(dh),
+                                  None if dx is None else _ptr(dx), _ptr(dbr), _ptr(partial), B, hidden, inp, H, W, D,
+                                  axis, int(bool(dx_add)), dtype, _stream(aq)), "sep_gru_dgrad")
+    return ar, dbr
+
+
+def gru_wgrad_slabs(inp: int, B: int, H: int, W: int, D: int, axis: int):
+    """(K-blocks, K-blocks per slab, slabs) of dvc_gru_wgrad's split-K (include/dvccorr.h): a K-block is
+    GRU_WGRAD_LINES lines x GRU_WGRAD_POS positions along the axis, positions fastest."""
+    length = (H, W, D)[axis]
+    nkb = -(-(B * H * W * D // length) // _lib.GRU_WGRAD_LINES) * -(-length // _lib.GRU_WGRAD_POS)
+    want = min(nkb, -(-_lib.GRU_WGRAD_TARGET // (3 * -(-(_lib.GRU_HIDDEN + inp) // 16))))
+    per = -(-nkb // want)
+    return nkb, per, -(-nkb // per)
+
+
+@_on_device
+def gru_wgrad(h: torch.Tensor, x: torch.Tensor, r: torch.Tensor, az: torch.Tensor, ar: torch.Tensor,
+              aq: torch.Tensor, axis: int, dtype: int) -> torch.Tensor:
+    """(3, hidden, hidden + input, 5) float32: the weight gradients of the z, r and q convolutions of one axis pass
+    (dvc_gru_wgrad) from the pass's input h, x, its reset gate r and the gate gradients a_z, a_r, a_q."""
+    B, hidden, H, W, D = _gru_tensors("gru_wgrad", (h, r, az, ar, aq), x)
+    inp = int(x.shape[1])
+    nws = lib().dvc_gru_wgrad_workspace_bytes(hidden, inp, B, H, W, D, axis)
+    if nws == 0:
+        raise NotImplementedError(f"gru_wgrad: hidden={hidden} input={inp} is outside the kernel's shapes "
+                                  f"(hidden {_lib.GRU_HIDDEN}, input 1..{_lib.GRU_MAX_INPUT})")
+    dw = torch.empty((3, hidden, hidden + inp, 5), dtype=torch.float32, device=h.device)
+    ws = torch.empty(nws // 4, dtype=torch.float32, device=h.device)
+    check(lib().dvc_gru_wgrad(*map(_ptr, (h, x, r, az, ar, aq, dw, ws)), B, hidden, inp, H, W, D, axis, dtype,
+                              _stream(h)), "gru_wgrad")
+    return dw
 
 
 def _conv_operand(t: torch.Tensor, what: str) -> None:

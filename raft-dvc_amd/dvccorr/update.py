@@ -13,9 +13,10 @@ Precision follows resolve_precision: "fp16" / "bf16" (also inside a CUDA autocas
 Trainer's AMP) round the operands once and accumulate in fp32; "fp32" splits them into bf16 hi + lo pieces (fp32
 tolerance 1e-5).  The gates, the blend and the returned hidden state are float32 in every precision.
 
-Forward only: inputs or weights that require grad (with grad enabled) raise NotImplementedError.  The kernel covers
-hidden 96 and input <= 160 (the reference model: 96 and 147); other channel counts run the same composition as
-F.conv3d calls on the GPU.
+sep_conv_gru and SepConvGRU are forward only: inputs or weights that require grad (with grad enabled) raise
+NotImplementedError.  sep_conv_gru_ad is the same GRU with a backward (csrc/gru_grad.hip: the gradients of h, x and
+the eighteen parameters) for training.  The kernels cover hidden 96 and input <= 160 (the reference model: 96 and
+147); other channel counts run the same composition as F.conv3d calls on the GPU.
 
 The whole of BasicUpdateBlock.forward (update.py:316-348): the motion encoder's convf1 / convf2 / conv and the flow
 and uncertainty heads run on k_conv7_flow / k_conv3_mfma (csrc/conv3.hip), with no library convolution and no
@@ -38,7 +39,7 @@ import torch.nn.functional as F
 from . import _lib, ops
 from .corr_block import _wants_grad, resolve_precision
 
-__all__ = ["SepConvGRU", "sep_conv_gru", "GRU_WEIGHT_NAMES", "UpdateBlock", "conv3x3x3", "conv3x3x3_ad"]
+__all__ = ["SepConvGRU", "sep_conv_gru", "sep_conv_gru_ad", "GRU_WEIGHT_NAMES", "UpdateBlock", "conv3x3x3", "conv3x3x3_ad"]
 
 _AXES = (("h", (2, 0, 0)), ("w", (0, 2, 0)), ("d", (0, 0, 2)))
 GRU_WEIGHT_NAMES = tuple(f"conv{g}_{ax}.{kind}" for ax, _ in _AXES for g in "zrq" for kind in ("weight", "bias"))
@@ -65,8 +66,9 @@ def _validate(h: torch.Tensor, x: torch.Tensor, weights: Mapping[str, torch.Tens
 
 def _refuse_grad(h, x, weights, names=GRU_WEIGHT_NAMES, what="sep_conv_gru", ref="SepConvGRU3D", more=()) -> None:
     if _wants_grad(h, x, *more, *(weights[n] for n in names)):
-        raise NotImplementedError(f"dvccorr.{what} has no backward; call it under torch.no_grad() or use the "
-                                  f"reference's {ref} for gradients")
+        hint = "dvccorr.sep_conv_gru_ad" if what == "sep_conv_gru" else f"the reference's {ref}"
+        raise NotImplementedError(f"dvccorr.{what} has no backward; call it under torch.no_grad() or use {hint} "
+                                  "for gradients")
 
 
 class _PackCache:
@@ -96,10 +98,12 @@ def kernel_covers(hidden: int, inp: int) -> bool:
     return hidden == _lib.GRU_HIDDEN and 1 <= inp <= _lib.GRU_MAX_INPUT
 
 
-def _composition(h: torch.Tensor, x: torch.Tensor, weights: Mapping[str, torch.Tensor]) -> torch.Tensor:
-    """The reference's nine convolutions in float32, for channel counts outside the kernel's."""
-    p = {n: weights[n].detach().float() for n in GRU_WEIGHT_NAMES}
-    h, x = h.detach().float(), x.detach().float()
+def _composition(h: torch.Tensor, x: torch.Tensor, weights: Mapping[str, torch.Tensor], detach: bool = True) -> torch.Tensor:
+    """The reference's nine convolutions in float32, for channel counts outside the kernel's (detach = False: with
+    autograd on, for sep_conv_gru_ad)."""
+    cut = (lambda t: t.detach().float()) if detach else (lambda t: t.float())
+    p = {n: cut(weights[n]) for n in GRU_WEIGHT_NAMES}
+    h, x = cut(h), cut(x)
     with torch.autocast("cuda", enabled=False):
         for ax, pad in _AXES:
             hx = torch.cat([h, x], dim=1)
@@ -126,6 +130,27 @@ def sep_conv_gru(h: torch.Tensor, x: torch.Tensor, weights: Mapping[str, torch.T
     """SepConvGRU3D.forward(h, x) with the module's state_dict() `weights`; returns the new hidden state (float32).
     Packs the weights on every call: keep a SepConvGRU where the same weights serve many calls."""
     return _run(h, x, weights, precision, lambda dtype: ops.gru_pack(weights, dtype))
+
+
+def sep_conv_gru_ad(h: torch.Tensor, x: torch.Tensor, weights: Mapping[str, torch.Tensor], *,
+                    precision: Optional[str] = None) -> torch.Tensor:
+    """sep_conv_gru as a differentiable function: SepConvGRU3D.forward(h, x), float32 out, bit-identical to
+    sep_conv_gru's, with gradients for h, x and the eighteen parameters (dvccorr::sep_gru_ad).  The training forward
+    (k_sep_gru_pass with SAVE) keeps z, r and q of the three passes and the two intermediate hidden states for the
+    backward: 11 x 96 x B H W D floats, 138 MB at 32^3.  The backward runs, per pass in reverse, k_gru_grad_prep,
+    k_sep_gru_dgrad (two launches) and k_gru_wgrad, skipping what no input asks for.  Precision as sep_conv_gru, in
+    both directions: "fp16" / "bf16" round both operands of every product once and accumulate in fp32, "fp32" splits
+    them into bf16 hi + lo pieces.  Under "fp16" the gate gradients are operands and are rounded to fp16 too, as the
+    reference's AMP backward does: scale the loss (GradScaler) so that they stay in fp16's range.  The packed weights
+    are cached per weight object until it changes (an optimiser step re-packs).  No double backward.  Channel counts
+    outside the kernels' (hidden 96, input <= 160) run the float32 composition with autograd on."""
+    _validate(h, x, weights)
+    ws = [weights[n] for n in GRU_WEIGHT_NAMES]
+    ops._need_cuda(h, x, *ws)
+    if not kernel_covers(h.shape[1], x.shape[1]):
+        return _composition(h, x, weights, detach=False)
+    dtype = ops.dtype_code(resolve_precision(h, precision))
+    return torch.ops.dvccorr.sep_gru_ad(h, x, ws, dtype)[0]
 
 
 class SepConvGRU:
