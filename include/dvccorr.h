@@ -377,6 +377,33 @@ size_t dvc_conv3_wgrad_workspace_bytes(int cin, int cout, int B, int H, int W, i
 int dvc_conv3_wgrad(const float *src0, int c0, const float *src1, int c1, const float *g, int cout, float *dw,
                     void *workspace, int B, int H, int W, int D, int dtype, void *stream);
 
+/* The weight gradient of dvc_conv7_flow (csrc/conv7_grad.hip): encoder.convf1 trains.  flow (B, 3, H, W, D) and g
+ * (B, DVC_CONV7_COUT, H, W, D) float32, contiguous; g = dL/dy [y > 0] and the bias gradient come from
+ * dvc_conv3_grad_prep with cout = DVC_CONV7_COUT.  The layer's input is the flow, which the model detaches at every
+ * iteration (raft_dvc.py:441): there is no input gradient.
+ *   dvc_conv7_wgrad       dw[o][ci][kh][kw][kd] = sum over (b, h, w, d) of g[b, o, h, w, d] flow[b, ci, h + kh - 3,
+ *               w + kw - 3, d + kd - 3] (out-of-volume flow is zero), the (64, 3, 7, 7, 7) float32 weight gradient,
+ *               as a GEMM over the voxels on the matrix cores.  The 3 * 343 = 1029 weights of an output channel are
+ *               the GEMM's columns, in 65 tiles of 16; a workgroup owns DVC_CONV7_WGRAD_TILES of them, so there are
+ *               groups = ceil(65 / TILES) workgroups per slab.  A K-block is a box of DVC_CONV7_WGRAD_KH x KW x KD
+ *               voxels; the nbox = B ceil(H / KH) ceil(W / KW) ceil(D / KD) blocks are cut into slabs of per =
+ *               ceil(nbox / min(nbox, ceil(DVC_CONV7_WGRAD_TARGET / groups))) consecutive blocks.  Each of the
+ *               ceil(nbox / per) slabs writes its partial dw to the workspace and the slabs are summed in index order
+ *               (no slab is empty; bit-identical from run to run).  dtype as dvc_conv7_flow; for DVC_F16 the
+ *               gradient operand g is rounded to fp16 too (scale the loss as under AMP).
+ *   dvc_conv7_wgrad_workspace_bytes   slabs * 64 * 1029 * 4 (0 for an empty or unsupported volume).
+ * No atomics, no allocation, no host synchronisation.  Errors, before any GPU call: a null pointer, B / H / W / D < 1,
+ * a bad dtype, or dw or the workspace overlapping an input or each other are DVC_ERR_INVALID; 2^31 voxels or more are
+ * DVC_ERR_UNSUPPORTED. */
+#define DVC_CONV7_WGRAD_KH 4
+#define DVC_CONV7_WGRAD_KW 4
+#define DVC_CONV7_WGRAD_KD 16
+#define DVC_CONV7_WGRAD_TILES 5
+#define DVC_CONV7_WGRAD_TARGET 256
+size_t dvc_conv7_wgrad_workspace_bytes(int B, int H, int W, int D);
+int dvc_conv7_wgrad(const float *flow, const float *g, float *dw, void *workspace, int B, int H, int W, int D,
+                    int dtype, void *stream);
+
 /* The backward of dvc_sep_gru_pass (csrc/gru_grad.hip).  All tensors (B, C, H, W, D) float32, contiguous; hidden is
  * DVC_GRU_HIDDEN, input 1..DVC_GRU_MAX_INPUT.  With G = dL/dh_out of one axis pass:
  *   dvc_sep_gru_pass_save   dvc_sep_gru_pass that also stores the pass's z, r and q (after tanh) into save, three

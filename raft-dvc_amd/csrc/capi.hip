@@ -102,6 +102,9 @@ hipError_t launch_conv3_wgrad(const float *src0, int c0, const float *src1, int 
                               void *workspace, int B, int H, int W, int D, int dtype, hipStream_t s);
 size_t conv7_packed_bytes(int dtype);
 hipError_t launch_conv7_pack(const float *w, const float *bias, void *packed, int dtype, hipStream_t s);
+size_t conv7_wgrad_workspace_bytes(int B, int H, int W, int D);
+hipError_t launch_conv7_wgrad(const float *flow, const float *g, float *dw, void *workspace, int B, int H, int W, int D,
+                              int dtype, hipStream_t s);
 hipError_t launch_conv7_flow(const float *flow, const void *packed, float *dst, int B, int H, int W, int D, int dtype,
                              hipStream_t s);
 }  // namespace dvc
@@ -1460,6 +1463,25 @@ int dvc_conv7_flow(const float *flow, const void *packed, float *dst, int B, int
     if (overlaps(dst, (size_t)vox * DVC_CONV7_COUT * 4, flow, (size_t)vox * 3 * 4))
         return fail(DVC_ERR_INVALID, "conv7_flow: dst must not overlap flow (a voxel reads its neighbours)");
     return launched("conv7_flow", launch_conv7_flow(flow, packed, dst, B, H, W, D, dtype, (hipStream_t)stream));
+}
+
+// the weight gradient of dvc_conv7_flow (conv7_grad.hip)
+size_t dvc_conv7_wgrad_workspace_bytes(int B, int H, int W, int D) {
+    if (volume_check("conv7_wgrad_workspace_bytes", B, H, W, D)) return 0;
+    return conv7_wgrad_workspace_bytes(B, H, W, D);
+}
+
+int dvc_conv7_wgrad(const float *flow, const float *g, float *dw, void *workspace, int B, int H, int W, int D,
+                    int dtype, void *stream) {
+    if (!flow || !g || !dw || !workspace) return fail(DVC_ERR_INVALID, "conv7_wgrad: null pointer");
+    if (int rc = volume_check("conv7_wgrad", B, H, W, D)) return rc;
+    if (int rc = dtype_ok("conv7_wgrad", dtype)) return rc;
+    const size_t vox = (size_t)B * H * W * D * 4;
+    const Span outs[2] = {{dw, (size_t)DVC_CONV7_COUT * 3 * 343 * 4}, {workspace, conv7_wgrad_workspace_bytes(B, H, W, D)}};
+    const Span ins[2] = {{flow, vox * 3}, {g, vox * DVC_CONV7_COUT}};
+    if (any_overlap(outs, 2, ins, 2))
+        return fail(DVC_ERR_INVALID, "conv7_wgrad: dw and the workspace must not overlap an input or each other");
+    return launched("conv7_wgrad", launch_conv7_wgrad(flow, g, dw, workspace, B, H, W, D, dtype, (hipStream_t)stream));
 }
 
 }  // extern "C"

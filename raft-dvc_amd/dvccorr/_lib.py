@@ -36,6 +36,7 @@ EXPORTED = (
     "dvc_conv3_pack_dgrad", "dvc_conv3_grad_prep", "dvc_conv3_wgrad_workspace_bytes", "dvc_conv3_wgrad",
     "dvc_sep_gru_pass_save", "dvc_gru_dgrad_packed_bytes", "dvc_gru_pack_dgrad", "dvc_gru_grad_prep",
     "dvc_sep_gru_dgrad", "dvc_gru_wgrad_workspace_bytes", "dvc_gru_wgrad",
+    "dvc_conv7_wgrad_workspace_bytes", "dvc_conv7_wgrad",
 )
 PROJ_COUT = 96          # DVC_PROJ_COUT (convc1 output channels, update.py:222)
 PROJ_MAX_RADIUS = 4     # DVC_PROJ_MAX_RADIUS
@@ -55,6 +56,12 @@ CONV3_PREP_CHUNK = 4096
 GRU_WGRAD_LINES, GRU_WGRAD_POS, GRU_WGRAD_TARGET = 32, 4, 512
 CONV7_TH, CONV7_TW, CONV7_TD = 4, 4, 16     # DVC_CONV7_TH / TW / TD: output box of one k_conv7_flow workgroup
 CONV7_COUT = 64         # DVC_CONV7_COUT (encoder.convf1, update.py:225)
+# DVC_CONV7_WGRAD_KH / KW / KD: the K-block (a voxel box) of k_conv7_wgrad; DVC_CONV7_WGRAD_TILES: the 16-column tiles of
+# the 1029 weight columns one workgroup owns; DVC_CONV7_WGRAD_TARGET: the workgroups its slab rule aims for
+# (ops.conv7_wgrad_slabs)
+CONV7_WGRAD_KH, CONV7_WGRAD_KW, CONV7_WGRAD_KD = 4, 4, 16
+CONV7_WGRAD_TILES = 5
+CONV7_WGRAD_TARGET = 256
 
 
 class Layout(ctypes.Structure):
@@ -143,6 +150,8 @@ def lib() -> ctypes.CDLL:
         "dvc_conv7_flow_packed_bytes": (sz, [i32]),
         "dvc_conv7_flow_pack": (i32, [vp, vp, vp, i32, vp]),
         "dvc_conv7_flow": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+        "dvc_conv7_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32]),
+        "dvc_conv7_wgrad": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
         "dvc_set_tuning": (i32, [ctypes.c_char_p, i32]),
         "dvc_last_error": (ctypes.c_char_p, []),
         "dvc_version": (ctypes.c_char_p, []),

@@ -30,6 +30,11 @@ the PyTorch dispatcher as named operators with shape functions:
         g, dtype) -> dW and dvccorr::conv3 on g with the transposed, flipped weights of dvccorr::conv3_pack_dgrad(weight,
         dtype) (a cached pack, no compute)
 
+    dvccorr::conv7_ad(flow, weight, bias, dtype) -> y   relu(convf1(flow)) as a differentiable op (update.py:225, 247):
+        forward dvccorr::conv7_flow's kernel into a new tensor; its registered backward is dvccorr::conv3_grad_prep
+        (mask from y, db) and dvccorr::conv7_wgrad(flow, g, dtype) -> dW (64, 3, 7, 7, 7).  The model detaches the flow
+        (raft_dvc.py:441); a flow that does require grad gets torch.nn.grad.conv3d_input of g in float32 (slow path)
+
     dvccorr::sep_gru_ad(h, x, weights[18], dtype) -> (h_out, saved)   SepConvGRU3D.forward as a differentiable op
         (update.py:167-199): the training forward keeps z, r, q of the three passes and the two intermediate hidden
         states in `saved` (non-differentiable); its registered backward runs, per pass and in reverse,
@@ -372,6 +377,71 @@ torch.library.register_autograd("dvccorr::conv3_ad", _conv3_ad_backward, setup_c
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# a differentiable encoder.convf1 (dvccorr.conv7x7x7_flow_ad): forward k_conv7_flow, backward csrc/conv7_grad.hip
+# ---------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("dvccorr::conv7_wgrad", mutates_args=())
+def conv7_wgrad(flow: Tensor, g: Tensor, dtype: int) -> Tensor:
+    return ops.conv7_wgrad(flow, g, dtype)
+
+
+@conv7_wgrad.register_fake
+def _(flow, g, dtype):
+    return flow.new_empty((g.shape[1], 3, 7, 7, 7), dtype=_F32)
+
+
+@torch.library.custom_op("dvccorr::conv7_ad", mutates_args=())
+def conv7_ad(flow: Tensor, weight: Tensor, bias: Tensor, dtype: int) -> Tensor:
+    """relu(conv7x7x7(flow) + bias) as a differentiable op: packs the weights (cached), allocates y and runs
+    dvc_conv7_flow.  weight and bias carry gradients (flow too, on a slow path)."""
+    flow = ops._f32c(flow)
+    if len(_conv3_packs()._entries) > _CONV3_AD_MAX_PACKS:
+        _conv3_packs()._entries.clear()
+    packed = _conv3_packs().get(("fwd7", id(weight), id(bias), dtype), (weight, bias),
+                                lambda: ops.conv7_flow_pack(weight, bias, dtype))
+    y = torch.empty((flow.shape[0], weight.shape[0]) + tuple(flow.shape[2:]), dtype=_F32, device=flow.device)
+    ops.conv7_flow(flow, packed, y, dtype)
+    return y
+
+
+@conv7_ad.register_fake
+def _(flow, weight, bias, dtype):
+    return flow.new_empty((flow.shape[0], weight.shape[0]) + tuple(flow.shape[2:]), dtype=_F32)
+
+
+def _conv7_ad_setup(ctx, inputs, output):
+    flow, weight, bias, dtype = inputs
+    ctx.save_for_backward(flow, weight, output)
+    ctx.dtype = int(dtype)
+    ctx.meta = (flow.dtype, weight.dtype, tuple(bias.shape), bias.dtype)
+
+
+def _conv7_ad_backward(ctx, grad_y):
+    """g = dL/dy [y > 0] (the mask from the op's own stored output) and db in one pass (dvccorr::conv3_grad_prep); dW
+    on k_conv7_wgrad (dvccorr::conv7_wgrad).  A flow that requires grad (the model's never does) gets
+    torch.nn.grad.conv3d_input of g in float32.  Whatever needs_input_grad does not ask for is skipped."""
+    if grad_y.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("dvccorr.conv7x7x7_flow_ad has no double backward")
+    flow, weight, y = ctx.saved_tensors
+    dtf, dtw, sb, dtb = ctx.meta
+    need_f, need_w, need_b = ctx.needs_input_grad[:3]
+    df = dw = db = None
+    if not (need_f or need_w or need_b):
+        return (None,) * 4
+    g, db_ = conv3_grad_prep(ops._f32c(grad_y), y, True)
+    if need_b:
+        db = db_.reshape(sb).to(dtb)
+    if need_w:
+        dw = conv7_wgrad(ops._f32c(flow), g, ctx.dtype).to(dtw)
+    if need_f:
+        with torch.autocast("cuda", enabled=False):
+            df = torch.nn.grad.conv3d_input(flow.shape, weight.detach().float(), g, padding=3).to(dtf)
+    return df, dw, db, None
+
+
+torch.library.register_autograd("dvccorr::conv7_ad", _conv7_ad_backward, setup_context=_conv7_ad_setup)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # a differentiable SepConvGRU3D (dvccorr.sep_conv_gru_ad): forward k_sep_gru_pass<SAVE>, backward csrc/gru_grad.hip
 # ---------------------------------------------------------------------------------------------------------------
 _GRU_NAMES = tuple(f"conv{g}_{ax}.{kind}" for ax in "hwd" for g in "zrq" for kind in ("weight", "bias"))
@@ -495,4 +565,4 @@ def _sep_gru_ad_backward(ctx, grad_h, _grad_saved=None):
 torch.library.register_autograd("dvccorr::sep_gru_ad", _sep_gru_ad_backward, setup_context=_sep_gru_ad_setup)
 
 
-__all__ = ["sep_gru_ad", "gru_pack_dgrad", "gru_grad_prep", "gru_dgrad", "gru_wgrad", "conv3_ad", "conv3_grad_prep", "conv3_wgrad", "conv3_pack_dgrad", "sep_gru", "conv3", "conv7_flow", "build", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "lookup_ad", "lookup_convc1_ad"]
+__all__ = ["conv7_ad", "conv7_wgrad", "sep_gru_ad", "gru_pack_dgrad", "gru_grad_prep", "gru_dgrad", "gru_wgrad", "conv3_ad", "conv3_grad_prep", "conv3_wgrad", "conv3_pack_dgrad", "sep_gru", "conv3", "conv7_flow", "build", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "lookup_ad", "lookup_convc1_ad"]

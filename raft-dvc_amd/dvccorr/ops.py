@@ -23,6 +23,7 @@ straight to libdvccorr.so (no CPU fallback).  Shapes follow include/dvccorr.h:
     conv3_pack_dgrad(weight, dtype)                    -> packed weights of the layer's input gradient (run by conv3)
     conv3_grad_prep(grad_y, y | None, relu)            -> (grad_y * (y > 0), its per-channel sums db)
     conv3_wgrad(x, x2 | None, g, dtype)                -> dW (Co, Ci, 3, 3, 3)  f32
+    conv7_wgrad(flow, g, dtype)                        -> dW (64, 3, 7, 7, 7)   f32   (encoder.convf1)
     sep_gru_save(h, x, packed, dtype)                  -> (h after the three passes, saved (11, B, 96, H, W, D))  f32
     gru_pack_dgrad(18 SepConvGRU3D tensors, dtype)     -> packed weights of the three passes' input gradients
     gru_grad_prep(g, z, q, h)                          -> (a_q, a_z, dh0, db_q, db_z) of one pass
@@ -757,6 +758,38 @@ def conv7_flow(flow: torch.Tensor, packed: torch.Tensor, dst: torch.Tensor, dtyp
     B, _, H, W, D = flow.shape
     check(lib().dvc_conv7_flow(_ptr(flow), _ptr(packed), _ptr(dst), B, H, W, D, dtype, _stream(flow)), "conv7_flow")
     return dst
+
+
+def conv7_wgrad_slabs(B: int, H: int, W: int, D: int):
+    """(K-blocks, K-blocks per slab, slabs) of dvc_conv7_wgrad's split-K (include/dvccorr.h): the K-blocks are the
+    CONV7_WGRAD_KH x KW x KD voxel boxes of the (B, H, W, D) grid in that order, D fastest."""
+    nbox = B * -(-H // _lib.CONV7_WGRAD_KH) * -(-W // _lib.CONV7_WGRAD_KW) * -(-D // _lib.CONV7_WGRAD_KD)
+    groups = -(-(-(-3 * 343 // 16)) // _lib.CONV7_WGRAD_TILES)
+    want = min(nbox, -(-_lib.CONV7_WGRAD_TARGET // groups))
+    per = -(-nbox // want)
+    return nbox, per, -(-nbox // per)
+
+
+@_on_device
+def conv7_wgrad(flow: torch.Tensor, g: torch.Tensor, dtype: int) -> torch.Tensor:
+    """dW (64, 3, 7, 7, 7) float32 of encoder.convf1 from its input flow (B, 3, H, W, D) and its masked output
+    gradient g (B, 64, H, W, D), both contiguous float32 (dvc_conv7_wgrad)."""
+    _need_cuda(flow, g)
+    _conv_operand(flow, "conv7_wgrad: flow")
+    _conv_operand(g, "conv7_wgrad: g")
+    if flow.ndim != 5 or g.ndim != 5 or flow.shape[1] != 3 or g.shape[1] != _lib.CONV7_COUT \
+            or g.shape[0] != flow.shape[0] or g.shape[2:] != flow.shape[2:]:
+        raise ValueError(f"conv7_wgrad: flow must be (B, 3, H, W, D) and g (B, {_lib.CONV7_COUT}, H, W, D); got "
+                         f"{tuple(flow.shape)} and {tuple(g.shape)}")
+    B, _, H, W, D = flow.shape
+    nws = lib().dvc_conv7_wgrad_workspace_bytes(B, H, W, D)
+    if nws == 0:
+        raise NotImplementedError(f"conv7_wgrad: B={B} volume {(H, W, D)} is outside the kernel's shapes")
+    dw = torch.empty((_lib.CONV7_COUT, 3, 7, 7, 7), dtype=torch.float32, device=flow.device)
+    ws = torch.empty(nws // 4, dtype=torch.float32, device=flow.device)
+    check(lib().dvc_conv7_wgrad(_ptr(flow), _ptr(g), _ptr(dw), _ptr(ws), B, H, W, D, dtype, _stream(flow)),
+          "conv7_wgrad")
+    return dw
 
 
 __all__ = ["pack_queries", "pack_targets", "pack_targets_gathered", "build", "pool", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "sample3d",

@@ -27,7 +27,12 @@ torch.cat per iteration:
     net, delta_flow, log_b = block(net, context, flow, cor=cor)  # raft_dvc.py:468
 
 conv3x3x3 is the functional form of one such layer, forward only; conv3x3x3_ad is the same layer with a backward
-(input, weight and bias gradients on csrc/conv3_grad.hip) for training.
+(input, weight and bias gradients on csrc/conv3_grad.hip) for training, conv7x7x7_flow_ad is encoder.convf1 with its
+weight and bias gradients (csrc/conv7_grad.hip), and update_block_ad is the whole block as one differentiable call:
+
+    cor = corr_fn.lookup_convc1(coords1, convc1.weight, convc1.bias)         # differentiable (lookup_convc1_ad)
+    net, delta_flow, log_b = dvccorr.update_block_ad(net, context, flow, update_block.state_dict(keep_vars=True),
+                                                     cor=cor)
 """
 from __future__ import annotations
 
@@ -39,7 +44,8 @@ import torch.nn.functional as F
 from . import _lib, ops
 from .corr_block import _wants_grad, resolve_precision
 
-__all__ = ["SepConvGRU", "sep_conv_gru", "sep_conv_gru_ad", "GRU_WEIGHT_NAMES", "UpdateBlock", "conv3x3x3", "conv3x3x3_ad"]
+__all__ = ["SepConvGRU", "sep_conv_gru", "sep_conv_gru_ad", "GRU_WEIGHT_NAMES", "UpdateBlock", "conv3x3x3", "conv3x3x3_ad",
+           "conv7x7x7_flow_ad", "update_block_ad"]
 
 _AXES = (("h", (2, 0, 0)), ("w", (0, 2, 0)), ("d", (0, 0, 2)))
 GRU_WEIGHT_NAMES = tuple(f"conv{g}_{ax}.{kind}" for ax, _ in _AXES for g in "zrq" for kind in ("weight", "bias"))
@@ -66,7 +72,8 @@ def _validate(h: torch.Tensor, x: torch.Tensor, weights: Mapping[str, torch.Tens
 
 def _refuse_grad(h, x, weights, names=GRU_WEIGHT_NAMES, what="sep_conv_gru", ref="SepConvGRU3D", more=()) -> None:
     if _wants_grad(h, x, *more, *(weights[n] for n in names)):
-        hint = "dvccorr.sep_conv_gru_ad" if what == "sep_conv_gru" else f"the reference's {ref}"
+        hint = {"sep_conv_gru": "dvccorr.sep_conv_gru_ad", "UpdateBlock": "dvccorr.update_block_ad"}.get(
+            what, f"the reference's {ref}")
         raise NotImplementedError(f"dvccorr.{what} has no backward; call it under torch.no_grad() or use {hint} "
                                   "for gradients")
 
@@ -281,6 +288,105 @@ def conv3x3x3_ad(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, *, r
     return torch.ops.dvccorr.conv3_ad(x, x2, weight, bias, bool(relu), dtype)
 
 
+def conv7x7x7_flow_ad(flow: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, *,
+                      precision: Optional[str] = None) -> torch.Tensor:
+    """encoder.convf1 as a differentiable function: relu(F.conv3d(flow, weight, bias, padding=3)) on the matrix cores,
+    float32 out (a new tensor), with gradients for weight and bias (dvccorr::conv7_ad).  The backward runs
+    k_conv3_grad_prep (ReLU mask from the op's own output, bias gradient) and k_conv7_wgrad (weight gradient),
+    skipping what no input asks for.  Precision as conv3x3x3_ad, in both directions; under "fp16" the incoming
+    gradient is an operand and is rounded to fp16 too: scale the loss (GradScaler).  The packed weights are cached per
+    weight object until it changes.  No double backward.  The model detaches the flow at every iteration
+    (raft_dvc.py:441); a flow that does require grad gets torch.nn.grad.conv3d_input of the masked gradient in
+    float32, a slow path.  Shapes other than (64, 3, 7, 7, 7) run F.conv3d in float32 with autograd on."""
+    _same_volume("conv7x7x7_flow", ("flow", flow))
+    if weight.ndim != 5 or tuple(weight.shape[1:]) != (flow.shape[1], 7, 7, 7) or tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError(f"conv7x7x7_flow: weight {tuple(weight.shape)} bias {tuple(bias.shape)} do not match "
+                         f"{flow.shape[1]} input channels of a 7 x 7 x 7 convolution")
+    ops._need_cuda(flow, weight, bias)
+    if tuple(weight.shape) != (_lib.CONV7_COUT, 3, 7, 7, 7) or not conv_covers(3, _lib.CONV7_COUT):
+        with torch.autocast("cuda", enabled=False):
+            return F.relu(F.conv3d(flow.float(), weight.float(), bias.float(), padding=3))
+    dtype = ops.dtype_code(resolve_precision(flow, precision))
+    return torch.ops.dvccorr.conv7_ad(flow, weight, bias, dtype)
+
+
+def _block_names(weights, what):
+    """(separable, has an uncertainty head, GRU names, all names) of a BasicUpdateBlock.state_dict()."""
+    separable = "gru.convz.weight" not in weights
+    gru_names = tuple("gru." + n for n in GRU_WEIGHT_NAMES) if separable else _wb(_CONVGRU_LAYERS)
+    has_unc = any(n.startswith("uncertainty_head.") for n in weights)
+    names = _wb(_ENCODER_LAYERS) + gru_names + _wb(_HEAD_LAYERS) + (_wb(_UNC_LAYERS) if has_unc else ())
+    missing = [n for n in names if n not in weights]
+    if missing:
+        raise ValueError(f"{what}: missing weights {missing} (BasicUpdateBlock.state_dict() names)")
+    return separable, has_unc, gru_names, names
+
+
+def _conv_ad(x, weight, bias, relu, precision, x2=None):
+    """A 3 x 3 x 3 layer of update_block_ad: the kernels where they cover it, else F.conv3d in float32 (autograd on)."""
+    if tuple(weight.shape[2:]) == (3, 3, 3):
+        return conv3x3x3_ad(x, weight, bias, relu=relu, precision=precision, x2=x2)
+    with torch.autocast("cuda", enabled=False):
+        xs = x.float() if x2 is None else torch.cat([x.float(), x2.float()], dim=1)
+        y = F.conv3d(xs, weight.float(), bias.float(), padding=tuple(k // 2 for k in weight.shape[2:]))
+        return F.relu(y) if relu else y
+
+
+def update_block_ad(net: torch.Tensor, context: torch.Tensor, flow: torch.Tensor, weights: Mapping[str, torch.Tensor],
+                    *, cor: Optional[torch.Tensor] = None, corr: Optional[torch.Tensor] = None,
+                    precision: Optional[str] = None):
+    """BasicUpdateBlock.forward (update.py:316-348) as a differentiable function of net, context, cor / corr and every
+    parameter in `weights` (the module's state_dict(keep_vars=True) names; the uncertainty head where present):
+
+        net, delta_flow, log_b = update_block_ad(net, context, flow, weights, cor=cor)
+
+    The composition of conv7x7x7_flow_ad (encoder.convf1), conv3x3x3_ad (convf2, conv with x2 = convf2's output, the
+    heads), torch.cat([context, motion, flow]) and sep_conv_gru_ad: every convolution runs on the HIP kernels in both
+    directions, and the forward values are bit-identical to UpdateBlock's in the same precision.  `cor` is
+    relu(convc1(corr)) from lookup_convc1 (differentiable there); a raw `corr` instead runs relu(F.conv3d(corr,
+    convc1)) in float32 with autograd on, the slow path.  The flow gets no gradient on the hot path (the model
+    detaches coords1, raft_dvc.py:441); one that requires grad takes conv7x7x7_flow_ad's slow path.  A non-separable
+    ConvGRU3D, or channel counts outside the kernels', run the float32 library composition with autograd on.  The
+    backward keeps the activations of every layer and the GRU's saved gates (sep_conv_gru_ad: 138 MB at 32^3); wrap
+    the call in torch.utils.checkpoint(..., use_reentrant=False) to recompute them instead.  No double backward."""
+    if (cor is None) == (corr is None):
+        raise ValueError("update_block_ad: pass exactly one of cor (= relu(convc1(corr)), from lookup_convc1) and corr")
+    separable, has_unc, gru_names, names = _block_names(weights, "update_block_ad")
+    feat = ("cor", cor) if cor is not None else ("corr", corr)
+    _same_volume("update_block_ad", ("net", net), ("context", context), ("flow", flow), feat)
+    w = lambda layer: (weights[layer + ".weight"], weights[layer + ".bias"])   # noqa: E731
+    cw = weights["encoder.conv.weight"]
+    cor_ch = int(weights["encoder.convc1.weight"].shape[0])
+    if flow.shape[1] != 3 or (cor is not None and cor.shape[1] != cor_ch) \
+            or cor_ch + weights["encoder.convf2.weight"].shape[0] != cw.shape[1]:
+        raise ValueError(f"update_block_ad: flow {tuple(flow.shape)} must have 3 channels and cor {cor_ch} "
+                         f"(encoder.conv reads {cw.shape[1]}); got {feat[0]} {tuple(feat[1].shape)}")
+    ops._need_cuda(net, context, flow, feat[1], *(weights[n] for n in names))
+    precision = resolve_precision(net, precision)
+    if cor is None:
+        with torch.autocast("cuda", enabled=False):
+            cw1, cb1 = w("encoder.convc1")
+            cor = F.relu(F.conv3d(corr.float(), cw1.float(), cb1.float()))
+    flo1 = conv7x7x7_flow_ad(flow, *w("encoder.convf1"), precision=precision)
+    flo2 = _conv_ad(flo1, *w("encoder.convf2"), True, precision)
+    mot = _conv_ad(cor, *w("encoder.conv"), True, precision, x2=flo2)
+    inp = torch.cat([context.float(), mot, flow.float()], dim=1)
+    if separable:
+        net = sep_conv_gru_ad(net, inp, {n[4:]: weights[n] for n in gru_names}, precision=precision)
+    else:
+        with torch.autocast("cuda", enabled=False):
+            h = net.float()
+            conv = lambda layer, x: F.conv3d(x, *(t.float() for t in w(layer)), padding=1)   # noqa: E731
+            hx = torch.cat([h, inp], dim=1)
+            z, r = torch.sigmoid(conv("gru.convz", hx)), torch.sigmoid(conv("gru.convr", hx))
+            q = torch.tanh(conv("gru.convq", torch.cat([r * h, inp], dim=1)))
+            net = (1 - z) * h + z * q
+
+    def head(prefix):
+        return _conv_ad(_conv_ad(net, *w(prefix + ".conv1"), True, precision), *w(prefix + ".conv2"), False, precision)
+    return net, head("flow_head"), (head("uncertainty_head") if has_unc else None)
+
+
 class UpdateBlock:
     """BasicUpdateBlock.forward (update.py:316-348) from the module's state_dict(): the motion encoder, the GRU and the
     flow head (and the uncertainty head where the state dict has one).
@@ -302,14 +408,7 @@ class UpdateBlock:
     Forward only: inputs or weights that require grad (with grad enabled) raise NotImplementedError."""
 
     def __init__(self, state_dict: Mapping[str, torch.Tensor], precision: Optional[str] = None):
-        self.separable = "gru.convz.weight" not in state_dict
-        gru_names = tuple("gru." + n for n in GRU_WEIGHT_NAMES) if self.separable else _wb(_CONVGRU_LAYERS)
-        self.has_uncertainty = any(n.startswith("uncertainty_head.") for n in state_dict)
-        self.names = _wb(_ENCODER_LAYERS) + gru_names + _wb(_HEAD_LAYERS) \
-            + (_wb(_UNC_LAYERS) if self.has_uncertainty else ())
-        missing = [n for n in self.names if n not in state_dict]
-        if missing:
-            raise ValueError(f"UpdateBlock: missing weights {missing} (BasicUpdateBlock.state_dict() names)")
+        self.separable, self.has_uncertainty, gru_names, self.names = _block_names(state_dict, "UpdateBlock")
         self.weights = state_dict
         self.precision = precision
         self.gru = SepConvGRU({n[4:]: state_dict[n] for n in gru_names}, precision) if self.separable else None
