@@ -342,6 +342,63 @@ int dvc_conv7_flow_pack(const float *w, const float *bias, void *packed, int dty
 int dvc_conv7_flow(const float *flow, const void *packed, float *dst, int B, int H, int W, int D, int dtype,
                    void *stream);
 
+/* The feature and context encoders' forward (csrc/encoder.hip; src/core/extractor.py:79-301, input_dim = 1, norms
+ * 'instance' and 'none').  Tensors are (B, C, H, W, D) float32, contiguous.  A convolution stores its raw output
+ * (+ bias) once; its InstanceNorm3d and ReLU are applied by the kernel that reads it, from a (B, C, 2) float32
+ * scale_shift = (1 / sqrt(var + eps), -mean scale) table.  An output extent is (n - 1) / stride + 1.
+ *   dvc_enc_stem   conv1: 1 -> DVC_ENC_STEM_COUT channels, 7 x 7 x 7, zero padding 3, stride 1 or 2, + bias; w
+ *               (32, 1, 7, 7, 7).
+ *   dvc_enc_conv   taps = 27 (3 x 3 x 3, zero padding 1) or 1 (1 x 1 x 1), stride 1 or 2, + bias.  prologue applied
+ *               to the input on load: DVC_ENC_IDENTITY, DVC_ENC_RELU, or DVC_ENC_NORM_RELU = relu(x scale + shift)
+ *               with scale_shift (B, cin, 2) (NULL: scale 1, shift 0); the zero padding belongs to the activated
+ *               tensor.  split < 0: y (B, cout, ..) gets the raw output.  0 < split < cout (the context encoder's
+ *               conv2): y (B, split, ..) gets tanh of channels [0, split), y2 (B, cout - split, ..) the ReLU of the
+ *               rest.
+ *   partials    where not NULL, the kernel writes dvc_enc_partials_bytes(taps, stride, cout, B, OH, OW, OD) bytes of
+ *               per-workgroup double sums of its output and its square ((taps, stride) = (343, stride) for the stem);
+ *               dvc_enc_stats reduces them in a fixed order (no atomics: bit-identical from run to run) into
+ *               scale_shift (B, cout, 2), biased variance.
+ *   dvc_enc_residual   out = relu(c3 scale3 + shift3 + r) over (B, C, H, W, D), r = shortcut (DVC_ENC_SC_PLAIN),
+ *               shortcut scale4 + shift4 (DVC_ENC_SC_NORM) or relu(shortcut scale4 + shift4) (DVC_ENC_SC_NORM_RELU);
+ *               a NULL table is scale 1, shift 0.  out must not overlap c3 or the shortcut.
+ * dtype: DVC_BF16 / DVC_F16 round the operands once, as dvc_conv3; DVC_F32 splits every operand into three bf16
+ * pieces (hi + mid + lo, the float32 value exactly) and takes six products per step, so only the float32
+ * accumulation rounds -- two pieces per operand, as dvc_conv3 uses, compound to 1e-4 over an encoder's twenty
+ * normalised layers.  The packed weights hold three pieces per fragment for DVC_F32.  No atomics, no allocation, no
+ * host synchronisation.
+ * Errors, before any GPU call: a null pointer, B / H / W / D < 1, a bad dtype, taps, stride, prologue, mode or
+ * split, or an output overlapping an input are DVC_ERR_INVALID; cin outside 8..DVC_ENC_MAX_CIN or no multiple of 8,
+ * cout outside 1..DVC_ENC_MAX_COUT, B * C > 65535 planes or 2^31 voxels or more are DVC_ERR_UNSUPPORTED (the size
+ * functions return 0 for all of these). */
+#define DVC_ENC_TH 4
+#define DVC_ENC_TW 4
+#define DVC_ENC_TD 16
+#define DVC_ENC_STEM_COUT 32
+#define DVC_ENC_MAX_CIN 128
+#define DVC_ENC_MAX_COUT 160
+#define DVC_ENC_IDENTITY 0
+#define DVC_ENC_RELU 1
+#define DVC_ENC_NORM_RELU 2
+#define DVC_ENC_SC_PLAIN 0
+#define DVC_ENC_SC_NORM 1
+#define DVC_ENC_SC_NORM_RELU 2
+size_t dvc_enc_stem_packed_bytes(int dtype);
+int dvc_enc_stem_pack(const float *w, const float *bias, void *packed, int dtype, void *stream);
+int dvc_enc_stem(const float *x, const void *packed, float *y, void *partials_or_null, int B, int H, int W, int D,
+                 int stride, int dtype, void *stream);
+size_t dvc_enc_conv_packed_bytes(int taps, int cin, int cout, int dtype);
+int dvc_enc_conv_pack(const float *w, const float *bias, void *packed, int taps, int cin, int cout, int dtype,
+                      void *stream);
+int dvc_enc_conv(const float *x, const float *scale_shift_or_null, int prologue, const void *packed, float *y,
+                 float *y2_or_null, int split, void *partials_or_null, int taps, int stride, int cin, int cout, int B,
+                 int H, int W, int D, int dtype, void *stream);
+size_t dvc_enc_partials_bytes(int taps, int stride, int cout, int B, int OH, int OW, int OD);
+int dvc_enc_stats(const void *partials, float *scale_shift, int taps, int stride, int cout, int B, int OH, int OW,
+                  int OD, float eps, void *stream);
+int dvc_enc_residual(const float *c3, const float *scale_shift3_or_null, const float *shortcut,
+                     const float *scale_shift4_or_null, int mode, float *out, int C, int B, int H, int W, int D,
+                     void *stream);
+
 /* The backward of dvc_conv3 (csrc/conv3_grad.hip).  With y = conv(cat[src0, src1], w) + bias (+ ReLU) and
  * g = dL/dy (times [y > 0] under ReLU), all (B, C, H, W, D) float32, contiguous:
  *   dvc_conv3_grad_prep   g = grad_y [y > 0] and db[o] = sum over (b, v) of g[b, o, v].  With ReLU pass y (the

@@ -107,6 +107,21 @@ hipError_t launch_conv7_wgrad(const float *flow, const float *g, float *dw, void
                               int dtype, hipStream_t s);
 hipError_t launch_conv7_flow(const float *flow, const void *packed, float *dst, int B, int H, int W, int D, int dtype,
                              hipStream_t s);
+long long enc_workgroups(int taps, int stride, int OH, int OW, int OD);
+size_t enc_stem_packed_bytes(int dtype);
+hipError_t launch_enc_stem_pack(const float *w, const float *bias, void *packed, int dtype, hipStream_t s);
+hipError_t launch_enc_stem(const float *x, const void *packed, float *y, void *partials, int B, int H, int W, int D,
+                           int stride, int dtype, hipStream_t s);
+size_t enc_conv_packed_bytes(int taps, int cin, int cout, int dtype);
+hipError_t launch_enc_conv_pack(const float *w, const float *bias, void *packed, int taps, int cin, int cout, int dtype,
+                                hipStream_t s);
+hipError_t launch_enc_conv(const float *x, const float *scale_shift, int prologue, const void *packed, float *y,
+                           float *y2, int split, void *partials, int taps, int stride, int cin, int cout, int B, int H,
+                           int W, int D, int dtype, hipStream_t s);
+hipError_t launch_enc_stats(const void *partials, float *scale_shift, int cout, int B, long long nwg, long long count,
+                            float eps, hipStream_t s);
+hipError_t launch_enc_residual(const float *c3, const float *ss3, const float *sc, const float *ss4, int mode,
+                               float *out, int planes, long long HWD, hipStream_t s);
 }  // namespace dvc
 
 using namespace dvc;
@@ -1390,6 +1405,124 @@ int dvc_conv3(const float *src0, int c0, const float *src1, int c1, const void *
         return fail(DVC_ERR_INVALID, "conv3: dst must not overlap a source (a voxel reads its neighbours)");
     return launched("conv3", launch_conv3(src0, c0, src1, c1, packed, dst, dst_channels, dst_offset, cout, relu != 0, B,
                                           H, W, D, dtype, (hipStream_t)stream));
+}
+
+// the encoders' forward (encoder.hip): the shapes k_enc_stem / k_enc_conv cover
+static int enc_kind_check(const char *what, int taps, int stride) {
+    if (taps != 1 && taps != 27 && taps != 343)
+        return fail(DVC_ERR_INVALID, "%s: taps=%d is not 1, 27 or 343 (the stem)", what, taps);
+    if (stride != 1 && stride != 2) return fail(DVC_ERR_INVALID, "%s: stride=%d is not 1 or 2", what, stride);
+    return DVC_OK;
+}
+
+static int enc_conv_shape_check(const char *what, int taps, int cin, int cout, int dtype) {
+    if (int rc = dtype_ok(what, dtype)) return rc;
+    if (taps != 1 && taps != 27) return fail(DVC_ERR_INVALID, "%s: taps=%d is not 1 or 27", what, taps);
+    if (cin < 1 || cout < 1) return fail(DVC_ERR_INVALID, "%s: cin=%d cout=%d", what, cin, cout);
+    if (cin % 8 != 0 || cin > DVC_ENC_MAX_CIN || cout > DVC_ENC_MAX_COUT)
+        return fail(DVC_ERR_UNSUPPORTED, "%s: cin=%d cout=%d (the kernel covers cin a multiple of 8 up to %d, cout 1..%d)",
+                    what, cin, cout, DVC_ENC_MAX_CIN, DVC_ENC_MAX_COUT);
+    return DVC_OK;
+}
+
+static inline int enc_extent(int n, int stride) { return (n - 1) / stride + 1; }
+
+size_t dvc_enc_stem_packed_bytes(int dtype) {
+    if (dtype_ok("enc_stem_packed_bytes", dtype)) return 0;
+    return enc_stem_packed_bytes(dtype);
+}
+
+int dvc_enc_stem_pack(const float *w, const float *bias, void *packed, int dtype, void *stream) {
+    if (!w || !bias || !packed) return fail(DVC_ERR_INVALID, "enc_stem_pack: null pointer");
+    if (int rc = dtype_ok("enc_stem_pack", dtype)) return rc;
+    return launched("enc_stem_pack", launch_enc_stem_pack(w, bias, packed, dtype, (hipStream_t)stream));
+}
+
+int dvc_enc_stem(const float *x, const void *packed, float *y, void *partials_or_null, int B, int H, int W, int D,
+                 int stride, int dtype, void *stream) {
+    if (!x || !packed || !y) return fail(DVC_ERR_INVALID, "enc_stem: null pointer");
+    if (int rc = dtype_ok("enc_stem", dtype)) return rc;
+    if (int rc = enc_kind_check("enc_stem", 343, stride)) return rc;
+    if (int rc = volume_check("enc_stem", B, H, W, D)) return rc;
+    const size_t ovox = (size_t)B * enc_extent(H, stride) * enc_extent(W, stride) * enc_extent(D, stride);
+    if (ovox * DVC_ENC_STEM_COUT >= (1ULL << 31))
+        return fail(DVC_ERR_UNSUPPORTED, "enc_stem: %zu output values exceed 32-bit indices", ovox * DVC_ENC_STEM_COUT);
+    if (overlaps(y, ovox * DVC_ENC_STEM_COUT * 4, x, (size_t)B * H * W * D * 4))
+        return fail(DVC_ERR_INVALID, "enc_stem: y must not overlap x");
+    return launched("enc_stem", launch_enc_stem(x, packed, y, partials_or_null, B, H, W, D, stride, dtype,
+                                                (hipStream_t)stream));
+}
+
+size_t dvc_enc_conv_packed_bytes(int taps, int cin, int cout, int dtype) {
+    if (enc_conv_shape_check("enc_conv_packed_bytes", taps, cin, cout, dtype)) return 0;
+    return enc_conv_packed_bytes(taps, cin, cout, dtype);
+}
+
+int dvc_enc_conv_pack(const float *w, const float *bias, void *packed, int taps, int cin, int cout, int dtype,
+                      void *stream) {
+    if (!w || !bias || !packed) return fail(DVC_ERR_INVALID, "enc_conv_pack: null pointer");
+    if (int rc = enc_conv_shape_check("enc_conv_pack", taps, cin, cout, dtype)) return rc;
+    return launched("enc_conv_pack", launch_enc_conv_pack(w, bias, packed, taps, cin, cout, dtype, (hipStream_t)stream));
+}
+
+int dvc_enc_conv(const float *x, const float *scale_shift_or_null, int prologue, const void *packed, float *y,
+                 float *y2_or_null, int split, void *partials_or_null, int taps, int stride, int cin, int cout, int B,
+                 int H, int W, int D, int dtype, void *stream) {
+    if (!x || !packed || !y) return fail(DVC_ERR_INVALID, "enc_conv: null pointer");
+    if (int rc = enc_conv_shape_check("enc_conv", taps, cin, cout, dtype)) return rc;
+    if (int rc = enc_kind_check("enc_conv", taps, stride)) return rc;
+    if (int rc = volume_check("enc_conv", B, H, W, D)) return rc;
+    if (prologue < DVC_ENC_IDENTITY || prologue > DVC_ENC_NORM_RELU)
+        return fail(DVC_ERR_INVALID, "enc_conv: prologue %d is not 0 (identity), 1 (ReLU) or 2 (norm + ReLU)", prologue);
+    if (split >= 0 && (split < 1 || split >= cout || !y2_or_null))
+        return fail(DVC_ERR_INVALID, "enc_conv: split=%d needs 0 < split < cout=%d and y2", split, cout);
+    const size_t ivox = (size_t)B * H * W * D;
+    const size_t ovox = (size_t)B * enc_extent(H, stride) * enc_extent(W, stride) * enc_extent(D, stride);
+    if (ivox * cin >= (1ULL << 33) || ovox * cout >= (1ULL << 33))
+        return fail(DVC_ERR_UNSUPPORTED, "enc_conv: tensors of 2^33 values or more");
+    const size_t yb = ovox * (split >= 0 ? split : cout) * 4, y2b = split >= 0 ? ovox * (cout - split) * 4 : 0;
+    if (overlaps(y, yb, x, ivox * cin * 4) || (y2b && (overlaps(y2_or_null, y2b, x, ivox * cin * 4) ||
+                                                       overlaps(y2_or_null, y2b, y, yb))))
+        return fail(DVC_ERR_INVALID, "enc_conv: an output must not overlap the input or the other output");
+    return launched("enc_conv", launch_enc_conv(x, scale_shift_or_null, prologue, packed, y, y2_or_null,
+                                                split >= 0 ? split : -1, partials_or_null, taps, stride, cin, cout, B, H,
+                                                W, D, dtype, (hipStream_t)stream));
+}
+
+size_t dvc_enc_partials_bytes(int taps, int stride, int cout, int B, int OH, int OW, int OD) {
+    if (enc_kind_check("enc_partials_bytes", taps, stride) || B < 1 || OH < 1 || OW < 1 || OD < 1 || cout < 1 ||
+        cout > DVC_ENC_MAX_COUT)
+        return 0;
+    return (size_t)B * enc_workgroups(taps, stride, OH, OW, OD) * cout * 2 * sizeof(double);
+}
+
+int dvc_enc_stats(const void *partials, float *scale_shift, int taps, int stride, int cout, int B, int OH, int OW,
+                  int OD, float eps, void *stream) {
+    if (!partials || !scale_shift) return fail(DVC_ERR_INVALID, "enc_stats: null pointer");
+    if (int rc = enc_kind_check("enc_stats", taps, stride)) return rc;
+    if (int rc = volume_check("enc_stats", B, OH, OW, OD)) return rc;
+    if (cout < 1 || !(eps >= 0.0f)) return fail(DVC_ERR_INVALID, "enc_stats: cout=%d eps=%g", cout, (double)eps);
+    if (cout > DVC_ENC_MAX_COUT)
+        return fail(DVC_ERR_UNSUPPORTED, "enc_stats: cout=%d (the kernels cover 1..%d)", cout, DVC_ENC_MAX_COUT);
+    return launched("enc_stats", launch_enc_stats(partials, scale_shift, cout, B, enc_workgroups(taps, stride, OH, OW, OD),
+                                                  (long long)OH * OW * OD, eps, (hipStream_t)stream));
+}
+
+int dvc_enc_residual(const float *c3, const float *scale_shift3_or_null, const float *shortcut,
+                     const float *scale_shift4_or_null, int mode, float *out, int C, int B, int H, int W, int D,
+                     void *stream) {
+    if (!c3 || !shortcut || !out) return fail(DVC_ERR_INVALID, "enc_residual: null pointer");
+    if (int rc = volume_check("enc_residual", B, H, W, D)) return rc;
+    if (C < 1) return fail(DVC_ERR_INVALID, "enc_residual: C=%d", C);
+    if (mode < DVC_ENC_SC_PLAIN || mode > DVC_ENC_SC_NORM_RELU)
+        return fail(DVC_ERR_INVALID, "enc_residual: mode %d is not 0 (plain), 1 (norm) or 2 (norm + ReLU)", mode);
+    if ((long long)B * C > 65535)
+        return fail(DVC_ERR_UNSUPPORTED, "enc_residual: %lld planes (B * C) exceed 65535", (long long)B * C);
+    const size_t nb = (size_t)B * C * H * W * D * 4;
+    if (overlaps(out, nb, c3, nb) || overlaps(out, nb, shortcut, nb))
+        return fail(DVC_ERR_INVALID, "enc_residual: out must not overlap c3 or the shortcut");
+    return launched("enc_residual", launch_enc_residual(c3, scale_shift3_or_null, shortcut, scale_shift4_or_null, mode,
+                                                        out, B * C, (long long)H * W * D, (hipStream_t)stream));
 }
 
 // the backward of dvc_conv3 (conv3_grad.hip)

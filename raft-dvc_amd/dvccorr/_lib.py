@@ -37,6 +37,9 @@ EXPORTED = (
     "dvc_sep_gru_pass_save", "dvc_gru_dgrad_packed_bytes", "dvc_gru_pack_dgrad", "dvc_gru_grad_prep",
     "dvc_sep_gru_dgrad", "dvc_gru_wgrad_workspace_bytes", "dvc_gru_wgrad",
     "dvc_conv7_wgrad_workspace_bytes", "dvc_conv7_wgrad",
+    "dvc_enc_stem_packed_bytes", "dvc_enc_stem_pack", "dvc_enc_stem",
+    "dvc_enc_conv_packed_bytes", "dvc_enc_conv_pack", "dvc_enc_conv",
+    "dvc_enc_partials_bytes", "dvc_enc_stats", "dvc_enc_residual",
 )
 PROJ_COUT = 96          # DVC_PROJ_COUT (convc1 output channels, update.py:222)
 PROJ_MAX_RADIUS = 4     # DVC_PROJ_MAX_RADIUS
@@ -62,6 +65,15 @@ CONV7_COUT = 64         # DVC_CONV7_COUT (encoder.convf1, update.py:225)
 CONV7_WGRAD_KH, CONV7_WGRAD_KW, CONV7_WGRAD_KD = 4, 4, 16
 CONV7_WGRAD_TILES = 5
 CONV7_WGRAD_TARGET = 256
+# the encoders' forward (csrc/encoder.hip): DVC_ENC_TH / TW / TD the output box of one workgroup (TW is 2 for the
+# strided 3 x 3 x 3 layers), DVC_ENC_STEM_COUT conv1's width, DVC_ENC_MAX_CIN / MAX_COUT the channel counts k_enc_conv
+# covers (cin a multiple of 8), and the prologue / shortcut modes
+ENC_TH, ENC_TW, ENC_TD = 4, 4, 16
+ENC_STEM_COUT = 32
+ENC_MAX_CIN, ENC_MAX_COUT = 128, 160
+ENC_IDENTITY, ENC_RELU, ENC_NORM_RELU = 0, 1, 2
+ENC_SC_PLAIN, ENC_SC_NORM, ENC_SC_NORM_RELU = 0, 1, 2
+ENC_STEM_TAPS = 343     # the stem's `taps` in dvc_enc_partials_bytes / dvc_enc_stats
 
 
 class Layout(ctypes.Structure):
@@ -152,6 +164,15 @@ def lib() -> ctypes.CDLL:
         "dvc_conv7_flow": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
         "dvc_conv7_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32]),
         "dvc_conv7_wgrad": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+        "dvc_enc_stem_packed_bytes": (sz, [i32]),
+        "dvc_enc_stem_pack": (i32, [vp, vp, vp, i32, vp]),
+        "dvc_enc_stem": (i32, [vp, vp, vp, vp] + [i32] * 6 + [vp]),
+        "dvc_enc_conv_packed_bytes": (sz, [i32, i32, i32, i32]),
+        "dvc_enc_conv_pack": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+        "dvc_enc_conv": (i32, [vp, vp, i32, vp, vp, vp, i32, vp] + [i32] * 9 + [vp]),
+        "dvc_enc_partials_bytes": (sz, [i32] * 7),
+        "dvc_enc_stats": (i32, [vp, vp] + [i32] * 7 + [ctypes.c_float, vp]),
+        "dvc_enc_residual": (i32, [vp, vp, vp, vp, i32, vp] + [i32] * 5 + [vp]),
         "dvc_set_tuning": (i32, [ctypes.c_char_p, i32]),
         "dvc_last_error": (ctypes.c_char_p, []),
         "dvc_version": (ctypes.c_char_p, []),

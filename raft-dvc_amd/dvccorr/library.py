@@ -43,6 +43,15 @@ the PyTorch dispatcher as named operators with shape functions:
         dvccorr::gru_pack_dgrad(weights, dtype) (a cached pack) and dvccorr::gru_wgrad(h, x, r, a_z, a_r, a_q, axis,
         dtype) -> dW of the pass's three convolutions
 
+    dvccorr::enc_stem(x, packed, y, partials?, stride, dtype)   y = conv1(x) + bias, raw         extractor.py:168, 239
+    dvccorr::enc_conv(x, scale_shift?, prologue, packed, y, y2?, partials?, taps, stride, dtype)   a bottleneck
+        convolution, the strided shortcut or conv2 with the producer's norm + ReLU applied on load   extractor.py:93-139
+    dvccorr::enc_conv_new(x, scale_shift?, prologue, packed, cout, split, taps, stride, dtype) -> (y, y2)   the same
+        into new tensors (conv2; split >= 0: the context encoder's tanh / ReLU halves, extractor.py:298-300)
+    dvccorr::enc_stats(partials, scale_shift, taps, stride, ovol, eps)   InstanceNorm3d's (scale, shift) per (b, c)
+    dvccorr::enc_residual(c3, ss3?, shortcut, ss4?, mode, out)   out = relu(norm3(c3) + shortcut)   extractor.py:131-137
+        (all forward only: no autograd formula is registered)
+
 Every op runs the HIP kernels of libdvccorr.so through ops.py (no CPU
 fallback); the fake (meta) implementations only compute output shapes, so the
 ops trace under torch.compile / FakeTensorMode and torch.library.opcheck.
@@ -252,6 +261,68 @@ def conv7_flow(flow: Tensor, packed: Tensor, dst: Tensor, dtype: int) -> None:
 @conv7_flow.register_fake
 def _(flow, packed, dst, dtype):
     return None
+
+
+# the encoders' forward (dvccorr.Encoder, csrc/encoder.hip): every kernel writes preallocated tensors
+@torch.library.custom_op("dvccorr::enc_stem", mutates_args=("y", "partials"))
+def enc_stem(x: Tensor, packed: Tensor, y: Tensor, partials: Optional[Tensor], stride: int, dtype: int) -> None:
+    ops.enc_stem(x, packed, y, partials, stride, dtype)
+
+
+@enc_stem.register_fake
+def _(x, packed, y, partials, stride, dtype):
+    return None
+
+
+@torch.library.custom_op("dvccorr::enc_conv", mutates_args=("y", "y2", "partials"))
+def enc_conv(x: Tensor, scale_shift: Optional[Tensor], prologue: int, packed: Tensor, y: Tensor, y2: Optional[Tensor],
+             partials: Optional[Tensor], taps: int, stride: int, dtype: int) -> None:
+    ops.enc_conv(x, scale_shift, prologue, packed, y, y2, partials, taps, stride, dtype)
+
+
+@enc_conv.register_fake
+def _(x, scale_shift, prologue, packed, y, y2, partials, taps, stride, dtype):
+    return None
+
+
+@torch.library.custom_op("dvccorr::enc_stats", mutates_args=("scale_shift",))
+def enc_stats(partials: Tensor, scale_shift: Tensor, taps: int, stride: int, ovol: Sequence[int], eps: float) -> None:
+    ops.enc_stats(partials, scale_shift, taps, stride, tuple(ovol), eps)
+
+
+@enc_stats.register_fake
+def _(partials, scale_shift, taps, stride, ovol, eps):
+    return None
+
+
+@torch.library.custom_op("dvccorr::enc_residual", mutates_args=("out",))
+def enc_residual(c3: Tensor, ss3: Optional[Tensor], shortcut: Tensor, ss4: Optional[Tensor], mode: int,
+                 out: Tensor) -> None:
+    ops.enc_residual(c3, ss3, shortcut, ss4, mode, out)
+
+
+@enc_residual.register_fake
+def _(c3, ss3, shortcut, ss4, mode, out):
+    return None
+
+
+@torch.library.custom_op("dvccorr::enc_conv_new", mutates_args=())
+def enc_conv_new(x: Tensor, scale_shift: Optional[Tensor], prologue: int, packed: Tensor, cout: int, split: int,
+                 taps: int, stride: int, dtype: int) -> tuple[Tensor, Tensor]:
+    """dvccorr::enc_conv into new tensors (the encoder's conv2, whose result is returned to the caller): (y, empty)
+    for split < 0, else (tanh of channels [0, split), ReLU of the rest)."""
+    ovol = ops.enc_out_volume(x.shape[2:], stride)
+    y = torch.empty((x.shape[0], cout if split < 0 else split) + ovol, dtype=_F32, device=x.device)
+    y2 = torch.empty((x.shape[0], 0 if split < 0 else cout - split) + ovol, dtype=_F32, device=x.device)
+    ops.enc_conv(x, scale_shift, prologue, packed, y, None if split < 0 else y2, None, taps, stride, dtype)
+    return y, y2
+
+
+@enc_conv_new.register_fake
+def _(x, scale_shift, prologue, packed, cout, split, taps, stride, dtype):
+    ovol = ops.enc_out_volume(x.shape[2:], stride)
+    return (x.new_empty((x.shape[0], cout if split < 0 else split) + ovol, dtype=_F32),
+            x.new_empty((x.shape[0], 0 if split < 0 else cout - split) + ovol, dtype=_F32))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -565,4 +636,4 @@ def _sep_gru_ad_backward(ctx, grad_h, _grad_saved=None):
 torch.library.register_autograd("dvccorr::sep_gru_ad", _sep_gru_ad_backward, setup_context=_sep_gru_ad_setup)
 
 
-__all__ = ["conv7_ad", "conv7_wgrad", "sep_gru_ad", "gru_pack_dgrad", "gru_grad_prep", "gru_dgrad", "gru_wgrad", "conv3_ad", "conv3_grad_prep", "conv3_wgrad", "conv3_pack_dgrad", "sep_gru", "conv3", "conv7_flow", "build", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "lookup_ad", "lookup_convc1_ad"]
+__all__ = ["enc_stem", "enc_conv", "enc_conv_new", "enc_stats", "enc_residual", "conv7_ad", "conv7_wgrad", "sep_gru_ad", "gru_pack_dgrad", "gru_grad_prep", "gru_dgrad", "gru_wgrad", "conv3_ad", "conv3_grad_prep", "conv3_wgrad", "conv3_pack_dgrad", "sep_gru", "conv3", "conv7_flow", "build", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "lookup_ad", "lookup_convc1_ad"]

@@ -29,6 +29,12 @@ straight to libdvccorr.so (no CPU fallback).  Shapes follow include/dvccorr.h:
     gru_grad_prep(g, z, q, h)                          -> (a_q, a_z, dh0, db_q, db_z) of one pass
     sep_gru_dgrad(a_q, a_z, h, r, packed_axis, dh, dx | None, axis, dx_add, dtype) -> (a_r, db_r); dh, dx in place
     gru_wgrad(h, x, r, a_z, a_r, a_q, axis, dtype)     -> dW (3, 96, 96 + Ci, 5) of one pass  f32
+    enc_stem_pack(weight (32, 1, 7, 7, 7), bias, dtype) / enc_stem(x, packed, y, partials | None, stride, dtype)
+    enc_conv_pack(weight (Co, Ci, 3 | 1, ..), bias, dtype) -> packed weights of one encoder convolution
+    enc_conv(x, scale_shift | None, prologue, packed, y, y2 | None, partials | None, taps, stride, dtype) -> y  f32
+    enc_partials(taps, stride, Co, B, ovol, device)    -> statistics partials buffer  f64
+    enc_stats(partials, scale_shift (B, C, 2), taps, stride, ovol, eps) -> scale_shift written  f32
+    enc_residual(c3, ss3 | None, shortcut, ss4 | None, mode, out) -> out = relu(norm3(c3) + shortcut)  f32
 """
 from __future__ import annotations
 
@@ -796,3 +802,172 @@ __all__ = ["pack_queries", "pack_targets", "pack_targets_gathered", "build", "po
            "proj_pack", "proj_pack_cached", "lookup_proj",
            "coords_grid", "upflow", "flow_step",
            "fused_workspace", "dtype_code", "layout", "bricked_levels", "DVC_BRICKED", "_lib"]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the encoders' forward (csrc/encoder.hip)
+# ---------------------------------------------------------------------------------------------------------------
+def enc_out_extent(n: int, stride: int) -> int:
+    """Output extent of a 7^3 / padding 3, 3^3 / padding 1 or 1^3 / padding 0 convolution with this stride."""
+    return (int(n) - 1) // int(stride) + 1
+
+
+def enc_out_volume(vol, stride: int):
+    return tuple(enc_out_extent(n, stride) for n in vol)
+
+
+def enc_covers(taps: int, cin: int, cout: int) -> bool:
+    """Channel counts k_enc_conv runs (dvc_enc_conv)."""
+    return taps in (1, 27) and cin % 8 == 0 and 8 <= cin <= _lib.ENC_MAX_CIN and 1 <= cout <= _lib.ENC_MAX_COUT
+
+
+def enc_partials(taps: int, stride: int, cout: int, B: int, ovol, device) -> torch.Tensor:
+    """The statistics partials buffer of one layer's output (dvc_enc_partials_bytes), as float64."""
+    n = lib().dvc_enc_partials_bytes(taps, stride, cout, B, *ovol)
+    if n == 0:
+        raise ValueError(f"enc_partials: taps={taps} stride={stride} cout={cout} B={B} volume {tuple(ovol)}")
+    return torch.empty(n // 8, dtype=torch.float64, device=device)
+
+
+@_on_device
+def enc_stem_pack(weight: torch.Tensor, bias: torch.Tensor, dtype: int) -> torch.Tensor:
+    """conv1's (32, 1, 7, 7, 7) weight and (32) bias -> the packed operands of dvc_enc_stem."""
+    _need_cuda(weight, bias)
+    if tuple(weight.shape) != (_lib.ENC_STEM_COUT, 1, 7, 7, 7) or tuple(bias.shape) != (_lib.ENC_STEM_COUT,):
+        raise NotImplementedError(f"enc_stem_pack: weight {tuple(weight.shape)} bias {tuple(bias.shape)}; the kernel "
+                                  f"covers ({_lib.ENC_STEM_COUT}, 1, 7, 7, 7)")
+    nbytes = lib().dvc_enc_stem_packed_bytes(dtype)
+    if nbytes == 0:
+        raise ValueError(f"enc_stem_pack: bad dtype {dtype}")
+    w, b = _f32c(weight.detach()), _f32c(bias.detach())
+    out = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
+    check(lib().dvc_enc_stem_pack(_ptr(w), _ptr(b), _ptr(out), dtype, _stream(w)), "enc_stem_pack")
+    return out
+
+
+def _enc_partials_ok(what, partials, taps, stride, cout, B, ovol) -> None:
+    if partials is None:
+        return
+    need = lib().dvc_enc_partials_bytes(taps, stride, cout, B, *ovol)
+    if partials.dtype != torch.float64 or not partials.is_contiguous() or _nbytes(partials) != need or need == 0:
+        raise ValueError(f"{what}: partials must be contiguous float64 of {need} bytes (enc_partials), got "
+                         f"{partials.dtype} of {_nbytes(partials)}")
+
+
+@_on_device
+def enc_stem(x: torch.Tensor, packed: torch.Tensor, y: torch.Tensor, partials, stride: int, dtype: int) -> torch.Tensor:
+    """y = conv1(x) + bias, raw: x (B, 1, H, W, D), y (B, 32, OH, OW, OD), contiguous float32 (dvc_enc_stem);
+    `partials` (enc_partials with taps = 343), where given, receives the statistics partials of y."""
+    _need_cuda(x, packed, y)
+    _conv_operand(x, "enc_stem: x")
+    _conv_operand(y, "enc_stem: y")
+    if stride not in (1, 2):
+        raise ValueError(f"enc_stem: stride {stride} is not 1 or 2")
+    if x.ndim != 5 or x.shape[1] != 1 or y.ndim != 5 or \
+            tuple(y.shape) != (x.shape[0], _lib.ENC_STEM_COUT) + enc_out_volume(x.shape[2:], stride):
+        raise ValueError(f"enc_stem: x must be (B, 1, H, W, D) and y (B, {_lib.ENC_STEM_COUT}, OH, OW, OD) of stride "
+                         f"{stride}; got {tuple(x.shape)} and {tuple(y.shape)}")
+    need = lib().dvc_enc_stem_packed_bytes(dtype)
+    _check_packed("enc_stem", packed, need, f"this precision takes {need} (enc_stem_pack with the same dtype)")
+    B, _, H, W, D = x.shape
+    _enc_partials_ok("enc_stem", partials, _lib.ENC_STEM_TAPS, stride, _lib.ENC_STEM_COUT, B, y.shape[2:])
+    check(lib().dvc_enc_stem(_ptr(x), _ptr(packed), _ptr(y), None if partials is None else _ptr(partials), B, H, W, D,
+                             stride, dtype, _stream(x)), "enc_stem")
+    return y
+
+
+@_on_device
+def enc_conv_pack(weight: torch.Tensor, bias: torch.Tensor, dtype: int) -> torch.Tensor:
+    """A (cout, cin, 3, 3, 3) or (cout, cin, 1, 1, 1) weight and its bias -> the packed operands of dvc_enc_conv."""
+    _need_cuda(weight, bias)
+    if weight.ndim != 5 or tuple(weight.shape[2:]) not in ((3, 3, 3), (1, 1, 1)) or \
+            tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError(f"enc_conv_pack: weight {tuple(weight.shape)} bias {tuple(bias.shape)} are not a 3 x 3 x 3 or "
+                         "1 x 1 x 1 convolution's")
+    cout, cin, taps = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2]) ** 3
+    nbytes = lib().dvc_enc_conv_packed_bytes(taps, cin, cout, dtype)
+    if nbytes == 0:
+        raise NotImplementedError(f"enc_conv_pack: cin={cin} cout={cout} is outside the kernel's shapes (cin a "
+                                  f"multiple of 8 up to {_lib.ENC_MAX_CIN}, cout 1..{_lib.ENC_MAX_COUT})")
+    w, b = _f32c(weight.detach()), _f32c(bias.detach())
+    out = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
+    check(lib().dvc_enc_conv_pack(_ptr(w), _ptr(b), _ptr(out), taps, cin, cout, dtype, _stream(w)), "enc_conv_pack")
+    return out
+
+
+@_on_device
+def enc_conv(x: torch.Tensor, scale_shift, prologue: int, packed: torch.Tensor, y: torch.Tensor, y2, partials,
+             taps: int, stride: int, dtype: int) -> torch.Tensor:
+    """y = conv(prologue(x)) + bias (dvc_enc_conv): taps 27 (3 x 3 x 3, padding 1) or 1, stride 1 or 2; prologue 0
+    identity, 1 ReLU, 2 relu(x scale + shift) with scale_shift (B, cin, 2).  With y2 the output is split (the
+    context encoder's conv2): y gets tanh of the first y.shape[1] channels, y2 the ReLU of the rest.  `partials`
+    (enc_partials), where given, receives the statistics partials of the raw output."""
+    ts = [x, y] + ([] if y2 is None else [y2]) + ([] if scale_shift is None else [scale_shift])
+    _need_cuda(packed, *ts)
+    for t in ts:
+        _conv_operand(t, "enc_conv: x, scale_shift, y and y2")
+    if taps not in (1, 27) or stride not in (1, 2) or prologue not in (0, 1, 2):
+        raise ValueError(f"enc_conv: taps {taps} (1 or 27), stride {stride} (1 or 2), prologue {prologue} (0, 1 or 2)")
+    if x.ndim != 5:
+        raise ValueError(f"enc_conv: x must be (B, C, H, W, D), got {tuple(x.shape)}")
+    B, cin, H, W, D = x.shape
+    ovol = enc_out_volume((H, W, D), stride)
+    for t in [y] + ([] if y2 is None else [y2]):
+        if t.ndim != 5 or t.shape[0] != B or tuple(t.shape[2:]) != ovol:
+            raise ValueError(f"enc_conv: an output of x {tuple(x.shape)} at stride {stride} must be (B, C) + {ovol}; "
+                             f"got {tuple(t.shape)}")
+    cout = int(y.shape[1]) + (0 if y2 is None else int(y2.shape[1]))
+    split = -1 if y2 is None else int(y.shape[1])
+    if scale_shift is not None and tuple(scale_shift.shape) != (B, cin, 2):
+        raise ValueError(f"enc_conv: scale_shift must be {(B, cin, 2)}, got {tuple(scale_shift.shape)}")
+    if prologue == 2 and scale_shift is None:
+        raise ValueError("enc_conv: prologue 2 needs scale_shift")
+    need = lib().dvc_enc_conv_packed_bytes(taps, cin, cout, dtype)
+    _check_packed("enc_conv", packed, need, f"taps {taps}, cin {cin}, cout {cout} and this precision take {need} "
+                  "(enc_conv_pack with the same dtype)")
+    _enc_partials_ok("enc_conv", partials, taps, stride, cout, B, ovol)
+    check(lib().dvc_enc_conv(_ptr(x), None if scale_shift is None else _ptr(scale_shift), prologue, _ptr(packed),
+                             _ptr(y), None if y2 is None else _ptr(y2), split,
+                             None if partials is None else _ptr(partials), taps, stride, cin, cout, B, H, W, D, dtype,
+                             _stream(x)), "enc_conv")
+    return y
+
+
+@_on_device
+def enc_stats(partials: torch.Tensor, scale_shift: torch.Tensor, taps: int, stride: int, ovol, eps: float) -> torch.Tensor:
+    """scale_shift (B, C, 2) <- (1 / sqrt(var + eps), -mean scale) per (b, c) from the partials of a layer's output
+    of volume ovol (dvc_enc_stats); taps and stride are the producing layer's (taps = 343: the stem)."""
+    _need_cuda(partials, scale_shift)
+    _conv_operand(scale_shift, "enc_stats: scale_shift")
+    if scale_shift.ndim != 3 or scale_shift.shape[2] != 2:
+        raise ValueError(f"enc_stats: scale_shift must be (B, C, 2), got {tuple(scale_shift.shape)}")
+    B, C, _ = scale_shift.shape
+    if partials is None:
+        raise ValueError("enc_stats: partials is None")
+    _enc_partials_ok("enc_stats", partials, taps, stride, C, B, ovol)
+    check(lib().dvc_enc_stats(_ptr(partials), _ptr(scale_shift), taps, stride, C, B, *[int(v) for v in ovol],
+                              float(eps), _stream(partials)), "enc_stats")
+    return scale_shift
+
+
+@_on_device
+def enc_residual(c3: torch.Tensor, ss3, shortcut: torch.Tensor, ss4, mode: int, out: torch.Tensor) -> torch.Tensor:
+    """out = relu(c3 scale3 + shift3 + r), r = shortcut (mode 0), shortcut scale4 + shift4 (1) or its ReLU (2); a
+    None table is scale 1, shift 0 (dvc_enc_residual).  All (B, C, H, W, D) contiguous float32."""
+    ts = [c3, shortcut, out] + [t for t in (ss3, ss4) if t is not None]
+    _need_cuda(*ts)
+    for t in ts:
+        _conv_operand(t, "enc_residual: tensors")
+    if c3.ndim != 5 or shortcut.shape != c3.shape or out.shape != c3.shape:
+        raise ValueError(f"enc_residual: c3, shortcut and out must be one (B, C, H, W, D) shape; got "
+                         f"{tuple(c3.shape)}, {tuple(shortcut.shape)}, {tuple(out.shape)}")
+    B, C, H, W, D = c3.shape
+    for t in (ss3, ss4):
+        if t is not None and tuple(t.shape) != (B, C, 2):
+            raise ValueError(f"enc_residual: a scale_shift table must be {(B, C, 2)}, got {tuple(t.shape)}")
+    if mode not in (0, 1, 2):
+        raise ValueError(f"enc_residual: mode {mode} is not 0, 1 or 2")
+    check(lib().dvc_enc_residual(_ptr(c3), None if ss3 is None else _ptr(ss3), _ptr(shortcut),
+                                 None if ss4 is None else _ptr(ss4), mode, _ptr(out), C, B, H, W, D, _stream(c3)),
+          "enc_residual")
+    return out
