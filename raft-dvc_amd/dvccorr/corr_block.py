@@ -44,6 +44,7 @@ does not fit.
 """
 from __future__ import annotations
 
+import functools
 import os
 from typing import List, Optional
 
@@ -394,15 +395,48 @@ def coords_grid_3d(batch: int, ht: int, wd: int, dp: int, device: torch.device) 
     return grid.unsqueeze(0).expand(batch, 3, ht, wd, dp).contiguous()
 
 
+@functools.lru_cache(maxsize=64)
+def _interp_matrix(n_out: int, n_in: int, device) -> torch.Tensor:
+    """(n_out, n_in) weights of linear align_corners=True interpolation along one axis, as k_upflow and ATen's
+    upsample_trilinear3d take them: ratio = float(in - 1) / (out - 1) (0 when out == 1), src = ratio * o,
+    i0 = trunc(src), i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1."""
+    ratio = torch.tensor((n_in - 1) / (n_out - 1) if n_out > 1 else 0.0, dtype=torch.float32)
+    src = ratio * torch.arange(n_out, dtype=torch.float32)
+    i0 = src.to(torch.int64)
+    i1 = i0 + (i0 < n_in - 1).to(torch.int64)
+    l1 = (src - i0.to(torch.float32)).clamp_(0.0, 1.0)
+    m = torch.zeros((n_out, n_in), dtype=torch.float32)
+    rows = torch.arange(n_out)
+    m[rows, i0] += 1.0 - l1
+    m[rows, i1] += l1
+    return m.to(device)
+
+
+def _interp_adjoint_ordered(g: torch.Tensor, lo_shape) -> torch.Tensor:
+    """The transpose of trilinear align_corners=True interpolation in a fixed summation order.  The interpolation is
+    the tensor product of three one-axis interpolations, so its transpose is applied axis by axis (d, w, h) as a
+    product with _interp_matrix and a sum over the fine axis."""
+    _, _, h, w, d = lo_shape
+    H, W, D = g.shape[2:]
+    for dim, (n_out, n_in) in ((4, (D, d)), (3, (W, w)), (2, (H, h))):
+        m = _interp_matrix(n_out, n_in, g.device)
+        g = (g.movedim(dim, -1).unsqueeze(-1) * m).sum(dim=-2).movedim(-1, dim)
+    return g.contiguous()
+
+
 def _upflow_adjoint(grad_up: torch.Tensor, lo_shape) -> torch.Tensor:
-    """Adjoint of upflow_3d: the per-axis scale of channels 0..2 (corr.py:242-251), then the
-    transpose of trilinear align_corners=True interpolation (ATen's upsample_trilinear3d_backward,
-    the op autograd runs for the reference's F.interpolate at corr.py:234-239)."""
+    """Adjoint of upflow_3d: the per-axis scale of channels 0..2 (corr.py:242-251), then the transpose of trilinear
+    align_corners=True interpolation (what autograd runs for the reference's F.interpolate at corr.py:234-239).  On the
+    CPU that is ATen's upsample_trilinear3d_backward, a sequential loop.  On the GPU the same ATen op scatters with
+    atomic adds, which made every gradient of a training step differ from run to run in its last bits (4e-6 of the
+    largest entry over three iterations): there the transpose runs in a fixed order (_interp_adjoint_ordered)."""
     B, C, h, w, d = lo_shape
     H, W, D = grad_up.shape[2:]
     g = grad_up.float().clone()
     for c, s in enumerate((H / h, W / w, D / d)[:min(C, 3)]):
         g[:, c] *= s
+    if g.is_cuda:
+        return _interp_adjoint_ordered(g, lo_shape)
     return torch.ops.aten.upsample_trilinear3d_backward(g, [H, W, D], [B, C, h, w, d], True, None, None, None)
 
 

@@ -174,27 +174,44 @@ def test_checkpoint():
 
 def test_two_training_iterations():
     """lookup_convc1 -> update_block_ad -> flow_step twice on 8^3 feature maps with coords1.detach() at the top of each
-    iteration (raft_dvc.py:441): finite, non-zero gradients for both feature maps and a convf1 weight."""
+    iteration (raft_dvc.py:441).  The loss (the mean end-point error of both upsampled flows: train_loop.sequence_loss
+    against a zero ground truth, gamma 1) and the gradients of both feature maps and of every parameter against the
+    float64 loop of tests/train_loop.py on the same inputs, which runs on the coordinates and ReLU decisions recorded
+    from the chain of ops (bit-identical to update_block_ad: test_backward_equals_the_chain_of_ops).  Bound:
+    (iters + 1) x 1e-5 = 3e-5 per tensor, as tests/test_gpu_train_loop.py derives it."""
     import dvccorr
+    import train_loop as tl
     B, vol, T = 1, (8, 8, 8), (16, 16, 16)
-    pd = {n: t.to(DEV).clone().requires_grad_(True) for n, t in uc.params().items()}
-    f1 = torch.from_numpy(prng.normal(9021, (B, 32, *vol))).to(DEV).requires_grad_(True)
-    f2 = torch.from_numpy(prng.normal(9022, (B, 32, *vol))).to(DEV).requires_grad_(True)
     c = uc.case("upd_888")
+    leaves = {"fmap1": torch.from_numpy(prng.normal(9021, (B, 32, *vol))),
+              "fmap2": torch.from_numpy(prng.normal(9022, (B, 32, *vol))), "net0": c["net0"], "context": c["context"]}
+    leaves.update(uc.params())
+    coords_init = torch.from_numpy(prng.identity_coords(B, *vol)) + _uniform(9023, (B, 3, *vol), 1.5)
+    gt = torch.zeros((B, 3) + T)
+    pd = {n: t.to(DEV).clone().requires_grad_(True) for n, t in uc.params().items()}
+    f1, f2 = leaves["fmap1"].to(DEV).requires_grad_(True), leaves["fmap2"].to(DEV).requires_grad_(True)
     net, ctx = c["net0"].to(DEV), c["context"].to(DEV)
     corr_fn = dvccorr.CorrBlock(f1, f2, 4, 4, precision="fp32")
     coords0 = dvccorr.coords_grid_3d(B, *vol, DEV)
-    coords1 = coords0 + _uniform(9023, (B, 3, *vol), 1.5).to(DEV)
-    loss = 0.0
+    coords1 = coords_init.to(DEV)
+    ups = []
     for it in range(2):
         coords1 = coords1.detach()
         cor = corr_fn.lookup_convc1(coords1, pd["encoder.convc1.weight"], pd["encoder.convc1.bias"])
         net, delta, _ = dvccorr.update_block_ad(net, ctx, coords1 - coords0, pd, cor=cor, precision="fp32")
         coords1, up = dvccorr.flow_step(coords1, delta, T)
-        loss = loss + up.abs().mean()
+        ups.append(up)
+    loss = tl.sequence_loss(ups, [], gt.to(DEV), 1.0)
     loss.backward()
-    for g in (f1.grad, f2.grad, pd["encoder.convf1.weight"].grad, pd["encoder.convc1.weight"].grad):
-        assert g is not None and torch.isfinite(g).all() and g.abs().max() > 0
+    got = {"fmap1": f1.grad, "fmap2": f2.grad, **{n: t.grad for n, t in pd.items()}}
+    _, agree, _, (rloss, want) = tl.against_float64(tl.HipOps("fp32", dvccorr.CorrBlock), leaves,
+                                                    {"coords_init": coords_init, "gt": gt}, T, 2, DEV, torch.float32,
+                                                    gamma=1.0, ref_gamma=1.0)
+    assert min(agree.values()) >= 0.999, agree
+    errs = {k: uc.err(got[k], want[k]) for k in got}
+    errs["loss"] = abs(float(loss.detach()) - float(rloss)) / abs(float(rloss))
+    print("two training iterations, worst:", max(errs.items(), key=lambda kv: kv[1]))
+    assert len(errs) == 2 + len(pd) + 1 and max(errs.values()) <= 3e-5, errs
 
 
 def _float64_grads(p, c, seeds, separable=True, corr=False):

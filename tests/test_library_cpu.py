@@ -72,6 +72,21 @@ def test_upflow_adjoint_matches_reference_autograd(lo, hi):
     torch.testing.assert_close(adj, flow.grad, rtol=1e-5, atol=1e-5)
 
 
+@pytest.mark.parametrize("lo,hi", [((4, 5, 6), (16, 20, 24)), ((8, 10, 12), (61, 77, 93)), ((3, 1, 5), (9, 4, 15))])
+def test_ordered_interp_adjoint_against_float64(lo, hi):
+    """The fixed-order transpose that the GPU takes (_interp_adjoint_ordered), run here on the CPU against float64
+    autograd of F.interpolate.  It sums axis by axis, not in ATen's order, so the bound is on the error normalised by
+    the largest entry: three float32 sums of at most ceil(out / in) + 1 <= 9 products each are <= 30 roundings of
+    2^-24, 2e-6."""
+    g = torch.Generator().manual_seed(sum(hi))
+    f64 = torch.randn(2, 4, *lo, generator=g, dtype=torch.float64, requires_grad=True)
+    gu = torch.randn(2, 4, *hi, generator=g)
+    (F.interpolate(f64, size=hi, mode="trilinear", align_corners=True) * gu.double()).sum().backward()
+    adj = corr_block._interp_adjoint_ordered(gu, tuple(f64.shape))
+    assert adj.dtype == torch.float32 and adj.shape == f64.shape and adj.is_contiguous()
+    assert float((adj.double() - f64.grad).abs().max() / f64.grad.abs().max()) <= 2e-6
+
+
 def test_backward_support_checked_at_construction():
     # any C: the gradient kernels run per 128-channel group (round 3; C = 256 trains like C = 128)
     corr_block._check_backward_support(dvccorr.layout(8, 8, 8, 2, 256), 256, 4, False)
