@@ -127,6 +127,12 @@ int dvc_layout_init(int H, int W, int D, int num_levels, int C, dvc_layout *out)
 /* Bit mask of the levels DVC_BRICKED stores in bricks (pure host function). */
 int dvc_bricked_levels(const dvc_layout *lay);
 
+/* How many trailing levels the dvc_corr_lookup call with these arguments stages whole in LDS (the tile kernel's
+ * coarse path, tuning "lookup_coarse") under the current tuning; 0 = none, -1 = bad arguments.  Pure host function,
+ * the rule the launch itself applies: for tests and tools. */
+int dvc_lookup_coarse_levels(int B, int64_t Nq, int H, int W, int D, int num_levels, int radius, int convention,
+                             int store_dtype);
+
 /* Bytes of float32 workspace dvc_pack_targets needs (pooled fmap2 levels 1..L-1; 0 for
  * num_levels <= 4, whose levels are pooled in LDS by one single-pass kernel). */
 size_t dvc_pack_workspace_bytes(int B, int C, int H, int W, int D, int num_levels);
@@ -515,6 +521,10 @@ int dvc_gru_wgrad(const float *h, const float *x, const float *r, const float *a
  * later launch of every host thread, on any stream, until set back.
  *   "lookup_variant" 2 = LDS-staged tile kernel (default), 0 = walk with unaligned
  *                    16-byte run loads, 1 = walk with aligned chunks + v_perm shifter;
+ *   "lookup_coarse"  the tile kernel's coarse levels (small enough to stage whole in LDS): 1 = staged
+ *                    whole, one unit per tile, dispatched first (default); 2 / 3 / 4 = the A/B
+ *                    variants (one unit per level and / or dispatched last); 0 = every level on
+ *                    the plane pipeline (bit-identical results for every value);
  *   "lookup_stretch" 1 = legacy W != D levels on k_lookup_stretch (LDS-staged stretched
  *                    boxes; the on-the-fly path on window-dot boxes), 0 = per-output
  *                    generic kernels (bit-identical results either way);

@@ -216,6 +216,7 @@ static int fill_lookup_args(LookupArgs &A, const dvc_layout &lay, const void *co
     A.trace = (unsigned long long *)(((unsigned long long)(unsigned)g_trace_hi << 32) | (unsigned)g_trace_lo);
     A.split_levels = 0;
     A.brick = 0;
+    A.ncoarse = 0; A.coarse_merge = 0; A.coarse_first = 0;
     return DVC_OK;
 }
 
@@ -260,6 +261,26 @@ static Knob<int> g_lookup_waves{4};
 // (-1 = the product's nontemporal stores; 0 plain, 16 sc1, 17 sc0 sc1, 18 nt sc1)
 static Knob<int> g_lookup_stpol{-1};
 
+// Coarse levels (lookup_coarse.h; tuning "lookup_coarse"): the trailing levels of a level-split launch that fit LDS
+// whole (coarse_level_ok: not zero, generic or bricked) are staged whole instead of plane by plane.  1 (default) =
+// those levels form one unit per tile, dispatched ahead of the fine levels' units; 2 = one unit per coarse level,
+// after the fine ones; 3 = one unit per tile, after; 4 = one per level, ahead; 0 = every level on the plane pipeline.
+// Bitwise-equal outputs for every value.  A/B at config #3 (tools/ab_lookup.py, medians of 100 calls, two runs):
+// 0 143.8 / 143.7 us, 2 136.4 / 137.3, 3 138.1 / 139.0, 4 131.3 / 131.4, 1 128.2 / 128.7.
+static Knob<int> g_lookup_coarse{1};
+
+// the trailing levels of a level-split launch that take the coarse path (A.split_levels, A.brick set)
+static int coarse_count(const LookupArgs &A, int esz) {
+    int k = 0;
+    if (!g_lookup_coarse || !A.split_levels || A.ablate) return 0;
+    for (int l = A.l0 + A.nl - 1; l >= A.l0; --l) {
+        if (A.zero[l] || A.generic[l] || ((A.brick >> l) & 1) || !coarse_level_ok(A.H[l], A.W[l], A.Dp[l], esz, A.r))
+            break;
+        ++k;
+    }
+    return k;
+}
+
 template <typename T, bool NT, int ACH>
 static void launch_tile_r(const LookupArgs &A, dim3 blocks, unsigned threads, hipStream_t s) {
     switch (A.r) {
@@ -281,7 +302,13 @@ static void launch_tile_nt(const LookupArgs &A0, hipStream_t s) {
     const int n = 2 * A.r + 1;
     const int ach = g_split_ach;
     const bool split_rows = NT && A.split_levels && tiles * A.nl < kSplitRows && n > ach && ach > 0;
-    const dim3 blocks((unsigned)tiles, A.split_levels ? (unsigned)A.nl : 1u,
+    const int cmode = g_lookup_coarse;
+    A.ncoarse = coarse_count(A, (int)sizeof(T));
+    A.coarse_merge = cmode == 1 || cmode == 3;
+    A.coarse_first = cmode == 1 || cmode == 4;
+    // units per tile: one per fine level, then the coarse levels' (one each, or one for all of them)
+    const int units = A.nl - A.ncoarse + (A.ncoarse > 0 && A.coarse_merge ? 1 : A.ncoarse);
+    const dim3 blocks((unsigned)tiles, A.split_levels ? (unsigned)units : 1u,
                       split_rows ? (unsigned)((n + ach - 1) / ach) : 1u);
     const bool bal = NT && A.r == 4 && g_lookup_waves == 4 && (ach == 5 || !split_rows);
     const unsigned threads = 64u * (bal ? 4u : (unsigned)((2 * A.r + 3) / 3));
@@ -450,6 +477,11 @@ int dvc_set_tuning(const char *key, int value) {
         if (value != -1 && value != 0 && value != 16 && value != 17 && value != 18)
             return fail(DVC_ERR_INVALID, "set_tuning: lookup_stpol %d (-1, 0, 16, 17 or 18)", value);
         g_lookup_stpol = value;
+        return DVC_OK;
+    }
+    if (!strcmp(key, "lookup_coarse")) {
+        if (value < 0 || value > 4) return fail(DVC_ERR_INVALID, "set_tuning: lookup_coarse %d (0..4)", value);
+        g_lookup_coarse = value;
         return DVC_OK;
     }
     if (!strcmp(key, "split_tiles")) {
@@ -962,6 +994,22 @@ int dvc_corr_lookup(const void *corr, const float *coords, float *out, int B, in
         }
     }
     return DVC_OK;
+}
+
+int dvc_lookup_coarse_levels(int B, int64_t Nq, int H, int W, int D, int num_levels, int radius, int convention,
+                             int store_dtype) {
+    dvc_layout lay;
+    if (dvc_layout_init(H, W, D, num_levels, 1, &lay) || B < 1 || Nq < 1 || radius < 0 || radius > 16) return -1;
+    const bool bricked = (store_dtype & DVC_BRICKED) != 0;
+    store_dtype &= ~DVC_BRICKED;
+    if (store_dtype != DVC_BF16 && store_dtype != DVC_F32 && store_dtype != DVC_F16) return -1;
+    LookupArgs A;
+    fill_lookup_args(A, lay, nullptr, nullptr, nullptr, B, Nq, radius, convention);
+    const int esz = store_dtype == DVC_F32 ? 4 : 2;
+    if (bricked) A.brick = dvc_bricked_levels(&lay);
+    if (lookup_variant() != 2 || !tile_ok(A, (size_t)esz)) return 0;
+    A.split_levels = (long long)A.B * A.nqb < g_split_tiles && A.nl > 1;   // as launch_tile_nt
+    return coarse_count(A, esz);
 }
 
 size_t dvc_proj_packed_bytes(int num_levels, int radius) {

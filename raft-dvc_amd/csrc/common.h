@@ -110,6 +110,10 @@ struct LookupArgs {
     int split_levels;              // tile kernel: one level per workgroup (blockIdx.y), for launches whose
                                    // query tiles alone cannot fill the chip (one rank's slab)
     int brick;                     // tile kernel: bit l = level l stored in (1, 8, 8) bricks (DVC_BRICKED)
+    int ncoarse;                   // tile kernel, level-split launches: the last ncoarse levels of [l0, l0 + nl) are
+                                   // staged whole (lookup_coarse.h); 0 = none
+    int coarse_merge;              // ... as one unit per tile (else one unit per level)
+    int coarse_first;              // ... dispatched ahead of the fine levels' units (else after them)
     long long off[DVC_MAX_LEVELS];
     // tile kernel with the motion encoder's convc1 fused (PROJ instances only):
     // packed bf16 weights (dvc_proj_pack), bias[96], out (B, 96, Nq)

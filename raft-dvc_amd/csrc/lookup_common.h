@@ -74,6 +74,25 @@ __device__ __forceinline__ void axis_weights(float p, float kp, int d, float sn,
     w0 = (k + 1.0f) - x;
 }
 
+// Coarse levels of the tile lookup (lookup_coarse.h): a level whose part of a pyramid row is at most
+// coarse_row_bytes(r) is staged whole for a 64-query tile, at that many bytes + kCoarsePad per query between two
+// guards.  The budget keeps the workgroups per CU that the instance's own plane slots allow in a CU's 160 KB of LDS:
+// radii 3, 4 (3 or 4 waves, two workgroups per CU) 1024 bytes -- an 8^3 level of a 16-bit pyramid, 66176 bytes of LDS
+// beside the 1.3 KB window table; r = 1, 2 (one or two waves) 256 bytes, which fits inside their own plane slots, so
+// their LDS size and their three waves per SIMD stay.
+// coarse_instance: the k_lookup_tile instances that carry the path -- 16-bit pyramids, r <= 4.  The fp32 instances
+// and radii 5, 6 sit at the 256-VGPR limit, and with the coarse body inlined beside it their plane pipeline spilled
+// more (compiler resource report: fp32 r = 4 four-wave 0 -> 8 VGPR spills, its row-split instance 4 -> 13, bf16 r = 5
+// row split 0 -> 7; config #2's fp32 step measured 2 % slower); out of line, the call convention spilled far more in
+// every instance.  Those instances are compiled without the path and keep their LDS size.
+constexpr int kCoarsePad = 8, kCoarseGuard = 64;
+constexpr bool coarse_instance(int esz, int r) { return esz == 2 && r >= 1 && r <= 4; }
+constexpr int coarse_row_bytes(int r) { return r <= 2 ? 256 : 1024; }
+constexpr int coarse_lds(int r) { return 2 * kCoarseGuard + 64 * (coarse_row_bytes(r) + kCoarsePad); }
+inline bool coarse_level_ok(int Hl, int Wl, int Dpl, int esz, int r) {
+    return coarse_instance(esz, r) && (long long)Hl * Wl * Dpl * esz <= coarse_row_bytes(r);
+}
+
 // Geometry of a legacy W != D level for k_lookup_stretch (lookup.hip), from the host: WX x DX the staged box of one
 // wave's chunk of W-axis samples (WX columns, DX values along D, RB bytes per staged row, LS bytes per lane's LDS
 // region); WINBUF (the on-the-fly path) reads a per-query window box of NYB x WXF x DX dots (boxe floats) instead of

@@ -170,6 +170,12 @@ template <int n> struct ZRun {
 struct ProjCfg {
     static constexpr int COUT = 96, OT = COUT / 16, KW = 32;
 };
+}  // namespace dvc
+
+#include "lookup_coarse.h"   // coarse_unit: small levels staged whole (uses lds_run, ZRun above)
+
+namespace dvc {
+
 // PROJ == 2 (round 5, fp32 blocks: the reference's fp32 evaluation path, evaluate_phase1.py:115-131): the same
 // consumer with every operand split into bf16 hi + lo (x = xh + xl + O(2^-16 x), w likewise) and three MFMAs per step,
 // xh wh + xl wh + xh wl: each product keeps ~2^-16 relative, well inside the fp32 tolerance 1e-5 on sums of
@@ -199,7 +205,10 @@ __global__ __launch_bounds__(64 * (TileCfg<T, R, NWV>::NWAVES + (PROJ ? 1 : 0)),
     constexpr int NU_LAST = n - C::COLS * (C::NWAVES - 1);   // output columns of the last wave
     constexpr int XROW = C::NWAVES * ProjCfg::KW * 2 + 16;    // bytes per query row of X (+16: bank spread)
     static_assert(!PROJ || C::COLS * n <= ProjCfg::KW, "PROJ: one wave's row values must fit a 32-k slice");
-    __shared__ __attribute__((aligned(16))) unsigned char smem[C::LDS];
+    // (the plain 16-bit instances of r <= 4 also run coarse levels, staged whole: lookup_coarse.h, coarse_instance)
+    constexpr bool COARSE = !PROJ && coarse_instance(C::ES, R);
+    constexpr int SMEM = (COARSE && coarse_lds(R) > C::LDS) ? coarse_lds(R) : C::LDS;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
     __shared__ int tab[5][64];   // per query of the tile: ih, cs, za, iv, iu (element units)
     __shared__ __attribute__((aligned(16))) unsigned char xs[PROJ ? PROJ * 64 * XROW : 16];   // X (PROJ 2: hi, lo)
     static_assert(PROJ != 2 || std::is_same<T, float>::value, "the split convc1 is the fp32 pyramid's");
@@ -345,6 +354,40 @@ __global__ __launch_bounds__(64 * (TileCfg<T, R, NWV>::NWAVES + (PROJ ? 1 : 0)),
         }
     };
     stamp(0);
+    // Units of a level-split launch (blockIdx.y): the fine levels one each, in level order, and the A.ncoarse
+    // trailing levels that fit LDS whole on the coarse path (lookup_coarse.h) -- one unit each, or one for all of
+    // them (A.coarse_merge); A.coarse_first dispatches the coarse units ahead of the fine ones.
+    int unit = (int)blockIdx.y;
+    if constexpr (COARSE) {
+        if (A.ncoarse > 0) {
+            const int nfine = A.nl - A.ncoarse, ncu = (int)gridDim.y - nfine;
+            if (A.coarse_first) unit = unit < ncu ? nfine + unit : unit - ncu;
+            if (unit >= nfine) {
+                const int lc0 = A.l0 + (A.coarse_merge ? nfine : unit);
+                const int lc1 = A.coarse_merge ? A.l0 + A.nl : lc0 + 1;
+                const int ca0 = ACH > 0 ? (int)blockIdx.z * ACH : 0;
+                const int ca1 = ACH > 0 ? min(ca0 + ACH, C::n) : C::n;
+                const int cu0 = BAL ? wave * FLO + min(wave, REM) : wave * C::COLS;
+                auto coarse = [&](auto nu_c) {
+                    coarse_unit<T, R, NT, ABL, SPOL, decltype(nu_c)::value, C::THREADS>(
+                        A, smem, lc0, lc1, cu0, ca0, ca1, b, qt, nvalid, stamp, [&]() {
+                            trace_level = 0;
+                            ++trace_li;
+                        });
+                };
+                if constexpr (BAL) {
+                    if (REM > 0 && wave < REM) coarse(std::integral_constant<int, FLO + 1>{});
+                    else coarse(std::integral_constant<int, FLO>{});
+                } else if (NU_LAST == C::COLS || wave < C::NWAVES - 1) {
+                    coarse(std::integral_constant<int, C::COLS>{});
+                } else {
+                    coarse(std::integral_constant<int, NU_LAST>{});
+                }
+                stamp(15);
+                return;
+            }
+        }
+    }
     // the coordinates first (the workgroup's first dependent memory round trip), the LDS clear under it
     float cy = 0.f, cx = 0.f, cz = 0.f;
     if (active) load_coords(A.coords, b, Nq, q, cy, cx, cz);
@@ -776,7 +819,7 @@ __global__ __launch_bounds__(64 * (TileCfg<T, R, NWV>::NWAVES + (PROJ ? 1 : 0)),
 
     // odd tiles walk the levels coarse-to-fine, so the two tiles sharing a CU mix the
     // gather-heavy fine levels with the store-heavy coarse ones
-    const int li0 = A.split_levels ? (int)blockIdx.y : 0;
+    const int li0 = A.split_levels ? unit : 0;
     const int li1 = A.split_levels ? li0 + 1 : A.nl;
     constexpr int NCH_A = ACH > 0 ? (n + ACH - 1) / ACH : 1;       // row chunks
     constexpr int NA_FULL = ACH > 0 ? ACH : n;

@@ -29,7 +29,7 @@ EXPORTED = (
     "dvc_corr_backward_workspace_bytes", "dvc_corr_backward_workspace_bytes_dtype", "dvc_corr_backward",
     "dvc_proj_packed_bytes", "dvc_proj_pack", "dvc_proj_pack_exact",
     "dvc_corr_lookup_proj", "dvc_lookup_fused_proj_workspace_bytes", "dvc_corr_lookup_fused_proj",
-    "dvc_coords_grid", "dvc_upflow", "dvc_flow_step", "dvc_bricked_levels", "dvc_corr_backward_mfma", "dvc_corr_backward_gout64",
+    "dvc_coords_grid", "dvc_upflow", "dvc_flow_step", "dvc_bricked_levels", "dvc_lookup_coarse_levels", "dvc_corr_backward_mfma", "dvc_corr_backward_gout64",
     "dvc_gru_packed_bytes", "dvc_gru_pack", "dvc_sep_gru_pass",
     "dvc_conv3_packed_bytes", "dvc_conv3_pack", "dvc_conv3",
     "dvc_conv7_flow_packed_bytes", "dvc_conv7_flow_pack", "dvc_conv7_flow",
@@ -116,6 +116,7 @@ def lib() -> ctypes.CDLL:
     sig = {
         "dvc_layout_init": (i32, [i32, i32, i32, i32, i32, ctypes.POINTER(Layout)]),
         "dvc_bricked_levels": (i32, [ctypes.POINTER(Layout)]),
+        "dvc_lookup_coarse_levels": (i32, [i32, ctypes.c_int64, i32, i32, i32, i32, i32, i32, i32]),
         "dvc_pack_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
         "dvc_pack_queries": (i32, [vp, vp, i32, i32, i64, i32, vp]),
         "dvc_pack_targets": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
@@ -210,6 +211,12 @@ def layout(H: int, W: int, D: int, num_levels: int, C: int = 1) -> Layout:
     if rc != DVC_OK:
         raise RuntimeError(lib().dvc_last_error().decode(errors="replace"))
     return lay
+
+
+def lookup_coarse_levels(B: int, Nq: int, H: int, W: int, D: int, num_levels: int, radius: int, legacy: bool,
+                         store_dtype: int) -> int:
+    """Trailing levels that dvc_corr_lookup with these arguments stages whole in LDS under the current tuning."""
+    return int(lib().dvc_lookup_coarse_levels(B, Nq, H, W, D, num_levels, radius, 1 if legacy else 0, store_dtype))
 
 
 def bricked_levels(lay: Layout) -> int:

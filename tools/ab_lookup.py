@@ -47,7 +47,8 @@ def apply(ks, reset=False):
         k, v = item.split("=")
         # (reset to the library defaults, not 0: lookup_waves is 4, split_tiles 1024, lookup_stpol -1)
         _lib.set_tuning(k, {"lookup_stpol": -1, "lookup_waves": 4, "split_tiles": 1024, "split_ach": 5,
-                            "lookup_variant": 2, "lookup_nt": 1, "lookup_order": 1}.get(k, 0) if reset else int(v))
+                            "lookup_variant": 2, "lookup_nt": 1, "lookup_order": 1,
+                            "lookup_coarse": 1}.get(k, 0) if reset else int(v))
 
 
 with torch.no_grad():
