@@ -405,6 +405,56 @@ int dvc_enc_residual(const float *c3, const float *scale_shift3_or_null, const f
                      const float *scale_shift4_or_null, int mode, float *out, int C, int B, int H, int W, int D,
                      void *stream);
 
+/* The backward of the encoders' forward (csrc/encoder_grad.hip): what dvccorr.encoder_ad needs.  For a layer
+ * y = conv(act(x)) + bias with cin -> cout channels, taps 27 or 1 (or 343: the stem, cin = 1, no prologue), stride 1 or
+ * 2, input volume (H, W, D), output volume (OH, OW, OD), and g_x = dL/dy (B, cout, OH, OW, OD):
+ *   dvc_enc_norm_grad   g_x from the gradient g with respect to the normalised value n = fma(x, scale, shift) of a raw
+ *               output x (B, C, H, W, D): gn = g [n > 0] (mask = 1) or g (mask = 0), g_x = scale (gn - mean(gn) -
+ *               n mean(gn n)), the means per (b, c) from per-workgroup double partials summed in index order.  With
+ *               scale_shift NULL (no norm) g_x = gn, the mask being [x > 0].  db (C), where not NULL, gets the sums
+ *               of g_x over (b, v), in a fixed order; gx may be NULL (db only).  partials: a work buffer of
+ *               dvc_enc_grad_partials_bytes(C, B, H, W, D) = B C ceil(H W D / DVC_ENC_GRAD_CHUNK) 3 doubles.
+ *   dvc_enc_grad_add    dst = (a + b) [m > 0] over n values; b and m may be NULL (dst may be a).
+ *   dvc_enc_split_grad  the gradient of the context encoder's conv2 output from its two halves: g (B, cout, ..) =
+ *               g_net (1 - net^2) on channels [0, split), g_ctx [ctx > 0] on the rest; a NULL gradient is zero.
+ *   dvc_enc_conv_pack_dgrad   the weights of the input gradient, W'[ci][o][t'] = w[o][ci][taps - 1 - t'], in
+ *               dvc_enc_conv_pack's layout (dvc_enc_dgrad_packed_bytes bytes); used with the dtype it was packed for.
+ *   dvc_enc_dgrad       dx (B, cin, H, W, D) = the transposed convolution of g_x: dvc_enc_conv's kernel at stride 1
+ *               on the packed dgrad weights; for stride 2 the source is read with zeros between its voxels.  cout
+ *               (the kernel's K) is a multiple of 8 up to DVC_ENC_MAX_COUT here, cin up to DVC_ENC_MAX_COUT.
+ *   dvc_enc_wgrad       dw[o][ci][t] = sum over (b, v) of g_x[b, o, v] act(x)[b, ci, v stride + delta(t)], the
+ *               (cout, cin, taps) float32 weight gradient as a split-K GEMM over the output voxels on the matrix
+ *               cores; the prologue as dvc_enc_conv (the zero padding belongs to the activated tensor).  A K step is
+ *               32 output voxels; the nk = B ceil(OH OW OD / 32) steps are cut into slabs of per = ceil(nk /
+ *               min(ceil(nk / 4), ceil(DVC_ENC_WGRAD_TARGET / groups))) steps, groups = ceil(ceil(taps cin / 16) /
+ *               (taps == 1 ? 2 : 7)) * ceil(cout / 32); each slab writes its partial to the workspace
+ *               (dvc_enc_wgrad_workspace_bytes = slabs * cout * cin * taps * 4) and the slabs are summed in index
+ *               order (bit-identical from run to run).
+ *   dvc_enc_stem_wgrad  the same for conv1: x (B, 1, H, W, D), dw (32, 1, 7, 7, 7).
+ * dtype as the forward; for DVC_F16 the gradient operands are rounded to fp16 too (scale the loss as under AMP).
+ * No atomics, no allocation, no host synchronisation.  Errors as dvc_enc_conv; channel counts outside the above are
+ * DVC_ERR_UNSUPPORTED (the _bytes functions return 0). */
+#define DVC_ENC_GRAD_CHUNK 4096
+#define DVC_ENC_WGRAD_TARGET 1024
+size_t dvc_enc_grad_partials_bytes(int C, int B, int H, int W, int D);
+int dvc_enc_norm_grad(const float *g, const float *x, const float *scale_shift_or_null, int mask, float *gx_or_null,
+                      float *db_or_null, void *partials, int C, int B, int H, int W, int D, void *stream);
+int dvc_enc_grad_add(const float *a, const float *b_or_null, const float *m_or_null, float *dst, long long n,
+                     void *stream);
+int dvc_enc_split_grad(const float *g_net_or_null, const float *g_ctx_or_null, const float *net, const float *ctx,
+                       float *g, int split, int cout, int B, int H, int W, int D, void *stream);
+size_t dvc_enc_dgrad_packed_bytes(int taps, int cin, int cout, int dtype);
+int dvc_enc_conv_pack_dgrad(const float *w, void *packed, int taps, int cin, int cout, int dtype, void *stream);
+int dvc_enc_dgrad(const float *g, const void *packed, float *dx, int taps, int stride, int cin, int cout, int B, int H,
+                  int W, int D, int dtype, void *stream);
+size_t dvc_enc_wgrad_workspace_bytes(int taps, int stride, int cin, int cout, int B, int H, int W, int D);
+int dvc_enc_wgrad(const float *x, const float *scale_shift_or_null, int prologue, const float *g, float *dw,
+                  void *workspace, int taps, int stride, int cin, int cout, int B, int H, int W, int D, int dtype,
+                  void *stream);
+size_t dvc_enc_stem_wgrad_workspace_bytes(int stride, int B, int H, int W, int D);
+int dvc_enc_stem_wgrad(const float *x, const float *g, float *dw, void *workspace, int stride, int B, int H, int W,
+                       int D, int dtype, void *stream);
+
 /* The backward of dvc_conv3 (csrc/conv3_grad.hip).  With y = conv(cat[src0, src1], w) + bias (+ ReLU) and
  * g = dL/dy (times [y > 0] under ReLU), all (B, C, H, W, D) float32, contiguous:
  *   dvc_conv3_grad_prep   g = grad_y [y > 0] and db[o] = sum over (b, v) of g[b, o, v].  With ReLU pass y (the

@@ -122,6 +122,21 @@ hipError_t launch_enc_stats(const void *partials, float *scale_shift, int cout, 
                             float eps, hipStream_t s);
 hipError_t launch_enc_residual(const float *c3, const float *ss3, const float *sc, const float *ss4, int mode,
                                float *out, int planes, long long HWD, hipStream_t s);
+size_t enc_grad_partials_bytes(int C, int B, long long HWD);
+hipError_t launch_enc_norm_grad(const float *g, const float *x, const float *scale_shift, int mask, float *gx, float *db,
+                                void *partials, int C, int B, long long HWD, hipStream_t s);
+hipError_t launch_enc_grad_add(const float *a, const float *b, const float *m, float *dst, long long n, hipStream_t s);
+hipError_t launch_enc_split_grad(const float *g_net, const float *g_ctx, const float *net, const float *ctx, float *g,
+                                 int split, int cout, int B, long long V, hipStream_t s);
+size_t enc_dgrad_packed_bytes(int taps, int cin, int cout, int dtype);
+hipError_t launch_enc_conv_pack_dgrad(const float *w, void *packed, int taps, int cin, int cout, int dtype,
+                                      hipStream_t s);
+hipError_t launch_enc_dgrad(const float *g, const void *packed, float *dx, int taps, int stride, int cin, int cout,
+                            int B, int H, int W, int D, int dtype, hipStream_t s);
+size_t enc_wgrad_workspace_bytes(int taps, int stride, int cin, int cout, int B, int H, int W, int D);
+hipError_t launch_enc_wgrad(const float *x, const float *scale_shift, int prologue, const float *g, float *dw,
+                            void *workspace, int taps, int stride, int cin, int cout, int B, int H, int W, int D,
+                            int dtype, hipStream_t s);
 }  // namespace dvc
 
 using namespace dvc;
@@ -1571,6 +1586,136 @@ int dvc_enc_residual(const float *c3, const float *scale_shift3_or_null, const f
         return fail(DVC_ERR_INVALID, "enc_residual: out must not overlap c3 or the shortcut");
     return launched("enc_residual", launch_enc_residual(c3, scale_shift3_or_null, shortcut, scale_shift4_or_null, mode,
                                                         out, B * C, (long long)H * W * D, (hipStream_t)stream));
+}
+
+// the encoders' backward (encoder_grad.hip)
+static int enc_grad_shape_check(const char *what, int taps, int cin, int cout, int dtype) {
+    if (int rc = dtype_ok(what, dtype)) return rc;
+    if (taps != 1 && taps != 27) return fail(DVC_ERR_INVALID, "%s: taps=%d is not 1 or 27", what, taps);
+    if (cin < 1 || cout < 1) return fail(DVC_ERR_INVALID, "%s: cin=%d cout=%d", what, cin, cout);
+    if (cin % 8 != 0 || cin > DVC_ENC_MAX_COUT || cout > DVC_ENC_MAX_COUT)
+        return fail(DVC_ERR_UNSUPPORTED, "%s: cin=%d cout=%d (the kernels cover cin a multiple of 8 and cout up to %d)",
+                    what, cin, cout, DVC_ENC_MAX_COUT);
+    return DVC_OK;
+}
+
+size_t dvc_enc_grad_partials_bytes(int C, int B, int H, int W, int D) {
+    if (C < 1 || volume_check("enc_grad_partials_bytes", B, H, W, D)) return 0;
+    return enc_grad_partials_bytes(C, B, (long long)H * W * D);
+}
+
+int dvc_enc_norm_grad(const float *g, const float *x, const float *scale_shift_or_null, int mask, float *gx_or_null,
+                      float *db_or_null, void *partials, int C, int B, int H, int W, int D, void *stream) {
+    if (!g || !partials || (!x && (scale_shift_or_null || mask)))
+        return fail(DVC_ERR_INVALID, "enc_norm_grad: null pointer");
+    if (!gx_or_null && !db_or_null) return fail(DVC_ERR_INVALID, "enc_norm_grad: neither gx nor db");
+    if (int rc = volume_check("enc_norm_grad", B, H, W, D)) return rc;
+    if (C < 1 || (mask != 0 && mask != 1)) return fail(DVC_ERR_INVALID, "enc_norm_grad: C=%d mask=%d", C, mask);
+    if ((long long)B * C > 65535)
+        return fail(DVC_ERR_UNSUPPORTED, "enc_norm_grad: %lld planes (B * C) exceed 65535", (long long)B * C);
+    const size_t nb = (size_t)B * C * H * W * D * 4;
+    if (gx_or_null && x && overlaps(gx_or_null, nb, x, nb))
+        return fail(DVC_ERR_INVALID, "enc_norm_grad: gx must not overlap x");
+    return launched("enc_norm_grad", launch_enc_norm_grad(g, x, scale_shift_or_null, mask, gx_or_null, db_or_null,
+                                                          partials, C, B, (long long)H * W * D, (hipStream_t)stream));
+}
+
+int dvc_enc_grad_add(const float *a, const float *b_or_null, const float *m_or_null, float *dst, long long n,
+                     void *stream) {
+    if (!a || !dst) return fail(DVC_ERR_INVALID, "enc_grad_add: null pointer");
+    if (n < 1) return fail(DVC_ERR_INVALID, "enc_grad_add: n=%lld", n);
+    return launched("enc_grad_add", launch_enc_grad_add(a, b_or_null, m_or_null, dst, n, (hipStream_t)stream));
+}
+
+int dvc_enc_split_grad(const float *g_net_or_null, const float *g_ctx_or_null, const float *net, const float *ctx,
+                       float *g, int split, int cout, int B, int H, int W, int D, void *stream) {
+    if (!net || !ctx || !g) return fail(DVC_ERR_INVALID, "enc_split_grad: null pointer");
+    if (int rc = volume_check("enc_split_grad", B, H, W, D)) return rc;
+    if (split < 1 || split >= cout) return fail(DVC_ERR_INVALID, "enc_split_grad: split=%d cout=%d", split, cout);
+    return launched("enc_split_grad", launch_enc_split_grad(g_net_or_null, g_ctx_or_null, net, ctx, g, split, cout, B,
+                                                            (long long)H * W * D, (hipStream_t)stream));
+}
+
+size_t dvc_enc_dgrad_packed_bytes(int taps, int cin, int cout, int dtype) {
+    // the layer with the channel counts swapped: cout is its K
+    if (enc_grad_shape_check("enc_dgrad_packed_bytes", taps, cout, cin, dtype)) return 0;
+    return enc_dgrad_packed_bytes(taps, cin, cout, dtype);
+}
+
+int dvc_enc_conv_pack_dgrad(const float *w, void *packed, int taps, int cin, int cout, int dtype, void *stream) {
+    if (!w || !packed) return fail(DVC_ERR_INVALID, "enc_conv_pack_dgrad: null pointer");
+    if (int rc = enc_grad_shape_check("enc_conv_pack_dgrad", taps, cout, cin, dtype)) return rc;
+    return launched("enc_conv_pack_dgrad", launch_enc_conv_pack_dgrad(w, packed, taps, cin, cout, dtype,
+                                                                      (hipStream_t)stream));
+}
+
+int dvc_enc_dgrad(const float *g, const void *packed, float *dx, int taps, int stride, int cin, int cout, int B, int H,
+                  int W, int D, int dtype, void *stream) {
+    if (!g || !packed || !dx) return fail(DVC_ERR_INVALID, "enc_dgrad: null pointer");
+    if (int rc = enc_grad_shape_check("enc_dgrad", taps, cout, cin, dtype)) return rc;
+    if (int rc = enc_kind_check("enc_dgrad", taps, stride)) return rc;
+    if (int rc = volume_check("enc_dgrad", B, H, W, D)) return rc;
+    const size_t ivox = (size_t)B * H * W * D;
+    const size_t ovox = (size_t)B * enc_extent(H, stride) * enc_extent(W, stride) * enc_extent(D, stride);
+    if (ivox * cin >= (1ULL << 33) || ovox * cout >= (1ULL << 33))
+        return fail(DVC_ERR_UNSUPPORTED, "enc_dgrad: tensors of 2^33 values or more");
+    if (overlaps(dx, ivox * cin * 4, g, ovox * cout * 4)) return fail(DVC_ERR_INVALID, "enc_dgrad: dx must not overlap g");
+    return launched("enc_dgrad", launch_enc_dgrad(g, packed, dx, taps, stride, cin, cout, B, H, W, D, dtype,
+                                                  (hipStream_t)stream));
+}
+
+static int enc_wgrad_check(const char *what, int taps, int stride, int cin, int cout, int B, int H, int W, int D,
+                           int dtype) {
+    if (int rc = dtype_ok(what, dtype)) return rc;
+    if (int rc = enc_kind_check(what, taps, stride)) return rc;
+    if (int rc = volume_check(what, B, H, W, D)) return rc;
+    if (cin < 1 || cout < 1) return fail(DVC_ERR_INVALID, "%s: cin=%d cout=%d", what, cin, cout);
+    if (taps == 343 ? (cin != 1 || cout != DVC_ENC_STEM_COUT)
+                    : (cin % 8 != 0 || cin > DVC_ENC_MAX_COUT || cout > DVC_ENC_MAX_COUT))
+        return fail(DVC_ERR_UNSUPPORTED, "%s: taps=%d cin=%d cout=%d (cin a multiple of 8 and cout up to %d; the stem 1 -> "
+                    "%d)", what, taps, cin, cout, DVC_ENC_MAX_COUT, DVC_ENC_STEM_COUT);
+    return DVC_OK;
+}
+
+size_t dvc_enc_wgrad_workspace_bytes(int taps, int stride, int cin, int cout, int B, int H, int W, int D) {
+    if (taps == 343 || enc_wgrad_check("enc_wgrad_workspace_bytes", taps, stride, cin, cout, B, H, W, D, DVC_F32)) return 0;
+    return enc_wgrad_workspace_bytes(taps, stride, cin, cout, B, H, W, D);
+}
+
+static int enc_wgrad_run(const char *what, const float *x, const float *ss, int prologue, const float *g, float *dw,
+                         void *workspace, int taps, int stride, int cin, int cout, int B, int H, int W, int D, int dtype,
+                         void *stream) {
+    if (!x || !g || !dw || !workspace) return fail(DVC_ERR_INVALID, "%s: null pointer", what);
+    if (int rc = enc_wgrad_check(what, taps, stride, cin, cout, B, H, W, D, dtype)) return rc;
+    if (prologue < DVC_ENC_IDENTITY || prologue > DVC_ENC_NORM_RELU || (prologue == DVC_ENC_NORM_RELU && !ss))
+        return fail(DVC_ERR_INVALID, "%s: prologue %d (0, 1, or 2 with a scale_shift table)", what, prologue);
+    const size_t wsb = enc_wgrad_workspace_bytes(taps, stride, cin, cout, B, H, W, D), dwb = (size_t)cout * cin * taps * 4;
+    const size_t xb = (size_t)B * cin * H * W * D * 4;
+    const size_t gb = (size_t)B * cout * enc_extent(H, stride) * enc_extent(W, stride) * enc_extent(D, stride) * 4;
+    if (overlaps(dw, dwb, workspace, wsb) || overlaps(dw, dwb, x, xb) || overlaps(dw, dwb, g, gb) ||
+        overlaps(workspace, wsb, x, xb) || overlaps(workspace, wsb, g, gb))
+        return fail(DVC_ERR_INVALID, "%s: dw and the workspace must not overlap an input or each other", what);
+    return launched(what, launch_enc_wgrad(x, prologue == DVC_ENC_NORM_RELU ? ss : nullptr, prologue, g, dw, workspace,
+                                           taps, stride, cin, cout, B, H, W, D, dtype, (hipStream_t)stream));
+}
+
+int dvc_enc_wgrad(const float *x, const float *scale_shift_or_null, int prologue, const float *g, float *dw,
+                  void *workspace, int taps, int stride, int cin, int cout, int B, int H, int W, int D, int dtype,
+                  void *stream) {
+    if (taps == 343) return fail(DVC_ERR_INVALID, "enc_wgrad: taps=343 is dvc_enc_stem_wgrad's");
+    return enc_wgrad_run("enc_wgrad", x, scale_shift_or_null, prologue, g, dw, workspace, taps, stride, cin, cout, B, H,
+                         W, D, dtype, stream);
+}
+
+size_t dvc_enc_stem_wgrad_workspace_bytes(int stride, int B, int H, int W, int D) {
+    if (enc_wgrad_check("enc_stem_wgrad_workspace_bytes", 343, stride, 1, DVC_ENC_STEM_COUT, B, H, W, D, DVC_F32)) return 0;
+    return enc_wgrad_workspace_bytes(343, stride, 1, DVC_ENC_STEM_COUT, B, H, W, D);
+}
+
+int dvc_enc_stem_wgrad(const float *x, const float *g, float *dw, void *workspace, int stride, int B, int H, int W,
+                       int D, int dtype, void *stream) {
+    return enc_wgrad_run("enc_stem_wgrad", x, nullptr, DVC_ENC_IDENTITY, g, dw, workspace, 343, stride, 1,
+                         DVC_ENC_STEM_COUT, B, H, W, D, dtype, stream);
 }
 
 // the backward of dvc_conv3 (conv3_grad.hip)

@@ -36,81 +36,11 @@
 // kept in LDS as float32 rows and a lane splits its eight values when it reads them (three 16-bit copies of the
 // strided 3 x 3 x 3 halo box would not fit).  Activations between kernels, statistics and outputs are float32 in
 // every precision.
-#include "mfma_conv.h"
+#include "enc_common.h"
 
 namespace dvc {
 
-constexpr int enc_pieces(int dtype) { return dtype == DVC_F32 ? 3 : 1; }
-
-// f(T{}, std::integral_constant<int, NP>{}) with the operand type and piece count of a DVC_* dtype
-template <typename F> inline void enc_with_precision(int dtype, F &&f) {
-    if (dtype == DVC_F32) f(bf16_t{}, std::integral_constant<int, 3>{});
-    else if (dtype == DVC_BF16) f(bf16_t{}, std::integral_constant<int, 1>{});
-    else f(f16_t{}, std::integral_constant<int, 1>{});
-}
-
-// one accumulator step: NP = 1 one product; NP = 3 the products a_i b_j with i + j <= 2, smallest first
-template <typename T, int NP>
-__device__ __forceinline__ f32x4 enc_mma(const u32x4 (&a)[NP], const u32x4 (&b)[NP], f32x4 d) {
-    if constexpr (NP == 3) {
-        d = mma16<T>(a[2], b[0], d);
-        d = mma16<T>(a[1], b[1], d);
-        d = mma16<T>(a[0], b[2], d);
-        d = mma16<T>(a[1], b[0], d);
-        d = mma16<T>(a[0], b[1], d);
-    }
-    return mma16<T>(a[0], b[0], d);
-}
-
-// eight fp32 values -> NP operand registers: each piece is the 16-bit rounding of what the pieces before it left
-// (the subtractions are exact)
-template <typename T, int NP> __device__ __forceinline__ void enc_split8(const float (&f)[8], u32x4 (&bf)[NP]) {
-    unsigned p[NP][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float a = f[2 * j], b = f[2 * j + 1];
-#pragma unroll
-        for (int pc = 0; pc < NP; ++pc) {
-            const unsigned h = pack2_16<T>(a, b);
-            p[pc][j] = h;
-            a -= bits16_to_f32<T>(h);
-            b -= bits16_to_f32<T>(h >> 16);
-        }
-    }
-#pragma unroll
-    for (int pc = 0; pc < NP; ++pc) bf[pc] = u32x4{p[pc][0], p[pc][1], p[pc][2], p[pc][3]};
-}
-
-// weight v -> value j of lane l of fragment fr: NP pieces, one kFragBytes behind the other
-template <typename T, int NP>
-__device__ __forceinline__ void enc_pack_store(unsigned char *out, int fr, int l, int j, float v) {
-    T *dst = reinterpret_cast<T *>(out + (long long)fr * NP * kFragBytes) + l * 8 + j;
-#pragma unroll
-    for (int pc = 0; pc < NP; ++pc) {
-        T h;
-        StoreT<T>::store(&h, v);
-        dst[pc * (kFragBytes / 2)] = h;
-        v -= StoreT<T>::load(&h);
-    }
-}
-
-constexpr int EN_TH = DVC_ENC_TH, EN_TD = DVC_ENC_TD;
 static_assert(EN_TH == 4 && EN_TD == 16, "one wave per output plane of the box, column groups of 16 voxels along D");
-
-// column groups per wave = output box extent along W
-constexpr int enc_tw(int taps, int stride) { return taps == 27 && stride == 2 ? 2 : DVC_ENC_TW; }
-// output tiles per workgroup and the packed tile count (a multiple of it)
-inline int enc_ntw(int taps, int cout) {
-    const int nt = (cout + 15) / 16;
-    return nt == 1 ? 1 : (nt == 2 || taps == 27) ? 2 : 4;
-}
-inline int enc_ntp(int taps, int cout) {
-    const int ntw = enc_ntw(taps, cout);
-    return ((cout + 15) / 16 + ntw - 1) / ntw * ntw;
-}
-inline int enc_out_extent(int n, int stride) { return (n - 1) / stride + 1; }
-inline int enc_nch(int taps, int cin) { return taps == 27 ? cin / 8 : (cin + 31) / 32; }
-inline int enc_ksteps(int taps) { return taps == 27 ? 7 : 1; }
 
 long long enc_workgroups(int taps, int stride, int OH, int OW, int OD) {
     const int tw = enc_tw(taps, stride);
@@ -329,10 +259,14 @@ struct EncConvArgs {
     EncOut E;
     long long HWD;
     int B, cin, H, W, D, prologue, nch, ntp, nth, ntw, ntd;
+    int SW, SD;               // ZI: the W and D extents of the stored source
 };
 
-template <typename T, int NP, int TAPS, int STRIDE, int NTW>
+// ZI (the input gradient of a strided layer, launch_enc_dgrad): the source is read as if zeros stood between its
+// voxels: virtual voxel (h, w, d) of the (H, W, D) volume is x[h / 2, w / 2, d / 2] where all three are even, else 0
+template <typename T, int NP, int TAPS, int STRIDE, int NTW, bool ZI = false>
 __global__ __launch_bounds__(256) void k_enc_conv(EncConvArgs A) {
+    static_assert(!ZI || STRIDE == 1, "the zero-inserted source is read at stride 1");
     constexpr int KS = TAPS == 27 ? 3 : 1, NG = enc_tw(TAPS, STRIDE);
     // staged rows: the halo box (TAPS = 27) or just the sampled voxels (TAPS = 1, RSTEP input voxels apart)
     constexpr int RH = TAPS == 27 ? (EN_TH - 1) * STRIDE + 3 : EN_TH, RW = TAPS == 27 ? (NG - 1) * STRIDE + 3 : NG,
@@ -366,7 +300,12 @@ __global__ __launch_bounds__(256) void k_enc_conv(EncConvArgs A) {
         const int h = h0 * STRIDE - KS / 2 + hh * RSTEP, w = w0 * STRIDE - KS / 2 + ww * RSTEP,
                   d = d0 * STRIDE - KS / 2 + dd * RSTEP;
         sok[i] = r < ROWS && h >= 0 && h < A.H && w >= 0 && w < A.W && d >= 0 && d < A.D;
-        soff[i] = sok[i] ? ((long long)h * A.W + w) * A.D + d : 0;
+        if constexpr (ZI) {
+            sok[i] = sok[i] && ((h | w | d) & 1) == 0;
+            soff[i] = sok[i] ? ((long long)(h >> 1) * A.SW + (w >> 1)) * A.SD + (d >> 1) : 0;
+        } else {
+            soff[i] = sok[i] ? ((long long)h * A.W + w) * A.D + d : 0;
+        }
     }
 
     float st[NST][CPC];
@@ -529,7 +468,7 @@ hipError_t launch_enc_conv(const float *x, const float *scale_shift, int prologu
     EncConvArgs A;
     A.x = x; A.ss = prologue == 2 ? scale_shift : nullptr; A.w = static_cast<const unsigned char *>(packed);
     A.HWD = (long long)H * W * D;
-    A.B = B; A.cin = cin; A.H = H; A.W = W; A.D = D; A.prologue = prologue;
+    A.B = B; A.cin = cin; A.H = H; A.W = W; A.D = D; A.prologue = prologue; A.SW = W; A.SD = D;
     A.nch = enc_nch(taps, cin); A.ntp = enc_ntp(taps, cout);
     const int OH = enc_out_extent(H, stride), OW = enc_out_extent(W, stride), OD = enc_out_extent(D, stride);
     const int tw = enc_tw(taps, stride);
@@ -545,6 +484,45 @@ hipError_t launch_enc_conv(const float *x, const float *scale_shift, int prologu
     } else {
         if (stride == 2) enc_conv_tiles<1, 2>(A, grid, ntw, dtype, s);
         else enc_conv_tiles<1, 1>(A, grid, ntw, dtype, s);
+    }
+    return hipGetLastError();
+}
+
+template <int TAPS, bool ZI> static void enc_dgrad_tiles(const EncConvArgs &A, dim3 grid, int ntw, int dtype, hipStream_t s) {
+    enc_with_precision(dtype, [&](auto t, auto np) {
+        using T = decltype(t);
+        constexpr int NP = decltype(np)::value;
+        if (ntw == 1) k_enc_conv<T, NP, TAPS, 1, 1, ZI><<<grid, 256, 0, s>>>(A);
+        else if (ntw == 2) k_enc_conv<T, NP, TAPS, 1, 2, ZI><<<grid, 256, 0, s>>>(A);
+        else if constexpr (TAPS == 1) k_enc_conv<T, NP, TAPS, 1, 4, ZI><<<grid, 256, 0, s>>>(A);
+    });
+}
+
+// The input gradient of a k_enc_conv layer (cin -> cout channels, input volume (H, W, D)): k_enc_conv at stride 1 on
+// g (B, cout, OH, OW, OD) with the transposed, flipped weights of k_enc_conv_pack_dgrad (encoder_grad.hip), zero
+// biases, no prologue; for a strided layer through the zero-inserted source.  dx (B, cin, H, W, D).  Arguments
+// validated by dvc_enc_dgrad (capi.hip).
+hipError_t launch_enc_dgrad(const float *g, const void *packed, float *dx, int taps, int stride, int cin, int cout,
+                            int B, int H, int W, int D, int dtype, hipStream_t s) {
+    EncConvArgs A;
+    const int OH = enc_out_extent(H, stride), OW = enc_out_extent(W, stride), OD = enc_out_extent(D, stride);
+    A.x = g; A.ss = nullptr; A.w = static_cast<const unsigned char *>(packed);
+    A.HWD = (long long)OH * OW * OD;
+    A.B = B; A.cin = cout; A.H = H; A.W = W; A.D = D; A.prologue = DVC_ENC_IDENTITY; A.SW = OW; A.SD = OD;
+    A.nch = enc_nch(taps, cout); A.ntp = enc_ntp(taps, cin);
+    const int tw = enc_tw(taps, 1);
+    A.nth = (H + EN_TH - 1) / EN_TH; A.ntw = (W + tw - 1) / tw; A.ntd = (D + EN_TD - 1) / EN_TD;
+    const long long nwg = (long long)A.nth * A.ntw * A.ntd;
+    fill_out(A.E, A.w, (size_t)A.nch * enc_ksteps(taps) * A.ntp * enc_pieces(dtype) * kFragBytes, dx, nullptr, -1, nullptr,
+             cin, H, W, D, nwg);
+    const int ntw = enc_ntw(taps, cin);
+    const dim3 grid((unsigned)(B * nwg), (unsigned)(A.ntp / ntw));
+    if (taps == 27) {
+        if (stride == 2) enc_dgrad_tiles<27, true>(A, grid, ntw, dtype, s);
+        else enc_dgrad_tiles<27, false>(A, grid, ntw, dtype, s);
+    } else {
+        if (stride == 2) enc_dgrad_tiles<1, true>(A, grid, ntw, dtype, s);
+        else enc_dgrad_tiles<1, false>(A, grid, ntw, dtype, s);
     }
     return hipGetLastError();
 }

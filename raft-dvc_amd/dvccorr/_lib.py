@@ -40,6 +40,9 @@ EXPORTED = (
     "dvc_enc_stem_packed_bytes", "dvc_enc_stem_pack", "dvc_enc_stem",
     "dvc_enc_conv_packed_bytes", "dvc_enc_conv_pack", "dvc_enc_conv",
     "dvc_enc_partials_bytes", "dvc_enc_stats", "dvc_enc_residual",
+    "dvc_enc_grad_partials_bytes", "dvc_enc_norm_grad", "dvc_enc_grad_add", "dvc_enc_split_grad",
+    "dvc_enc_dgrad_packed_bytes", "dvc_enc_conv_pack_dgrad", "dvc_enc_dgrad",
+    "dvc_enc_wgrad_workspace_bytes", "dvc_enc_wgrad", "dvc_enc_stem_wgrad_workspace_bytes", "dvc_enc_stem_wgrad",
 )
 PROJ_COUT = 96          # DVC_PROJ_COUT (convc1 output channels, update.py:222)
 PROJ_MAX_RADIUS = 4     # DVC_PROJ_MAX_RADIUS
@@ -74,6 +77,10 @@ ENC_MAX_CIN, ENC_MAX_COUT = 128, 160
 ENC_IDENTITY, ENC_RELU, ENC_NORM_RELU = 0, 1, 2
 ENC_SC_PLAIN, ENC_SC_NORM, ENC_SC_NORM_RELU = 0, 1, 2
 ENC_STEM_TAPS = 343     # the stem's `taps` in dvc_enc_partials_bytes / dvc_enc_stats
+# the encoders' backward (csrc/encoder_grad.hip): DVC_ENC_GRAD_CHUNK voxels per workgroup of the norm-gradient kernels,
+# DVC_ENC_WGRAD_TARGET the workgroups k_enc_wgrad's slab rule aims for
+ENC_GRAD_CHUNK = 4096
+ENC_WGRAD_TARGET = 1024
 
 
 class Layout(ctypes.Structure):
@@ -174,6 +181,17 @@ def lib() -> ctypes.CDLL:
         "dvc_enc_partials_bytes": (sz, [i32] * 7),
         "dvc_enc_stats": (i32, [vp, vp] + [i32] * 7 + [ctypes.c_float, vp]),
         "dvc_enc_residual": (i32, [vp, vp, vp, vp, i32, vp] + [i32] * 5 + [vp]),
+        "dvc_enc_grad_partials_bytes": (sz, [i32] * 5),
+        "dvc_enc_norm_grad": (i32, [vp, vp, vp, i32, vp, vp, vp] + [i32] * 5 + [vp]),
+        "dvc_enc_grad_add": (i32, [vp, vp, vp, vp, ctypes.c_longlong, vp]),
+        "dvc_enc_split_grad": (i32, [vp] * 5 + [i32] * 6 + [vp]),
+        "dvc_enc_dgrad_packed_bytes": (sz, [i32] * 4),
+        "dvc_enc_conv_pack_dgrad": (i32, [vp, vp] + [i32] * 4 + [vp]),
+        "dvc_enc_dgrad": (i32, [vp, vp, vp] + [i32] * 9 + [vp]),
+        "dvc_enc_wgrad_workspace_bytes": (sz, [i32] * 8),
+        "dvc_enc_wgrad": (i32, [vp, vp, i32, vp, vp, vp] + [i32] * 9 + [vp]),
+        "dvc_enc_stem_wgrad_workspace_bytes": (sz, [i32] * 5),
+        "dvc_enc_stem_wgrad": (i32, [vp, vp, vp, vp] + [i32] * 6 + [vp]),
         "dvc_set_tuning": (i32, [ctypes.c_char_p, i32]),
         "dvc_last_error": (ctypes.c_char_p, []),
         "dvc_version": (ctypes.c_char_p, []),

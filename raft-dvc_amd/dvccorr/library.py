@@ -636,4 +636,127 @@ def _sep_gru_ad_backward(ctx, grad_h, _grad_saved=None):
 torch.library.register_autograd("dvccorr::sep_gru_ad", _sep_gru_ad_backward, setup_context=_sep_gru_ad_setup)
 
 
-__all__ = ["enc_stem", "enc_conv", "enc_conv_new", "enc_stats", "enc_residual", "conv7_ad", "conv7_wgrad", "sep_gru_ad", "gru_pack_dgrad", "gru_grad_prep", "gru_dgrad", "gru_wgrad", "conv3_ad", "conv3_grad_prep", "conv3_wgrad", "conv3_pack_dgrad", "sep_gru", "conv3", "conv7_flow", "build", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "lookup_ad", "lookup_convc1_ad"]
+# ---------------------------------------------------------------------------------------------------------------
+# the encoders that train (dvccorr.encoder_ad / context_encoder_ad): forward csrc/encoder.hip into new tensors,
+# backward csrc/encoder_grad.hip
+# ---------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("dvccorr::enc_norm_grad", mutates_args=())
+def enc_norm_grad(g: Tensor, x: Optional[Tensor], scale_shift: Optional[Tensor], mask: bool, want_gx: bool,
+                  want_db: bool) -> tuple[Tensor, Tensor]:
+    """(g_x, db) of ops.enc_norm_grad; what is not asked for is an empty tensor."""
+    gx, db = ops.enc_norm_grad(ops._f32c(g), x, scale_shift, mask, want_gx, want_db)
+    return (g.new_empty(0) if gx is None else gx), (g.new_empty(0) if db is None else db)
+
+
+@enc_norm_grad.register_fake
+def _(g, x, scale_shift, mask, want_gx, want_db):
+    return (g.new_empty(g.shape if want_gx else (0,), dtype=_F32), g.new_empty((g.shape[1],) if want_db else (0,), dtype=_F32))
+
+
+@torch.library.custom_op("dvccorr::enc_grad_add", mutates_args=())
+def enc_grad_add(a: Tensor, b: Optional[Tensor], m: Optional[Tensor]) -> Tensor:
+    return ops.enc_grad_add(ops._f32c(a), b, m)
+
+
+@enc_grad_add.register_fake
+def _(a, b, m):
+    return a.new_empty(a.shape, dtype=_F32)
+
+
+@torch.library.custom_op("dvccorr::enc_split_grad", mutates_args=())
+def enc_split_grad(g_net: Optional[Tensor], g_ctx: Optional[Tensor], net: Tensor, ctx: Tensor) -> Tensor:
+    return ops.enc_split_grad(None if g_net is None else ops._f32c(g_net), None if g_ctx is None else ops._f32c(g_ctx),
+                              net, ctx)
+
+
+@enc_split_grad.register_fake
+def _(g_net, g_ctx, net, ctx):
+    return net.new_empty((net.shape[0], net.shape[1] + ctx.shape[1]) + tuple(net.shape[2:]), dtype=_F32)
+
+
+@torch.library.custom_op("dvccorr::enc_pack_dgrad", mutates_args=())
+def enc_pack_dgrad(weight: Tensor, dtype: int) -> Tensor:
+    """ops.enc_conv_pack_dgrad: the packed weights of an encoder convolution's input gradient (dvccorr.encoder_ad keeps
+    them in the weight set's pack cache; this operator packs anew)."""
+    return ops.enc_conv_pack_dgrad(weight, dtype)
+
+
+@enc_pack_dgrad.register_fake
+def _(weight, dtype):
+    cout, cin, taps = weight.shape[0], weight.shape[1], 27 if weight.shape[2] == 3 else 1
+    nt = (cin + 15) // 16
+    ntw = 1 if nt == 1 else 2 if (nt == 2 or taps == 27) else 4
+    ntp = (nt + ntw - 1) // ntw * ntw
+    units = (cout // 8) * 7 if taps == 27 else (cout + 31) // 32
+    return weight.new_empty((units * ntp * (3 if dtype == ops.DVC_F32 else 1) * 256 + 16 * ntp,), dtype=_F32)
+
+
+@torch.library.custom_op("dvccorr::enc_dgrad", mutates_args=())
+def enc_dgrad(g: Tensor, packed: Tensor, taps: int, stride: int, cin: int, vol: Sequence[int], dtype: int) -> Tensor:
+    return ops.enc_dgrad(g, packed, taps, stride, cin, tuple(vol), dtype)
+
+
+@enc_dgrad.register_fake
+def _(g, packed, taps, stride, cin, vol, dtype):
+    return g.new_empty((g.shape[0], cin) + tuple(vol), dtype=_F32)
+
+
+@torch.library.custom_op("dvccorr::enc_wgrad", mutates_args=())
+def enc_wgrad(x: Tensor, scale_shift: Optional[Tensor], prologue: int, g: Tensor, taps: int, stride: int,
+              dtype: int) -> Tensor:
+    return ops.enc_wgrad(x, scale_shift, prologue, g, taps, stride, dtype)
+
+
+@enc_wgrad.register_fake
+def _(x, scale_shift, prologue, g, taps, stride, dtype):
+    k = 1 if taps == 1 else 3 if taps == 27 else 7
+    return x.new_empty((g.shape[1], x.shape[1], k, k, k), dtype=_F32)
+
+
+@torch.library.custom_op("dvccorr::encoder_ad", mutates_args=())
+def encoder_ad(x: Tensor, weights: Sequence[Tensor], strides: Sequence[int], instance: bool, split: int, eps: float,
+               dtype: int) -> list[Tensor]:
+    """An encoder's forward as a differentiable op: [y, y2, *kept].  y is conv2's raw output (split < 0; y2 empty) or
+    its tanh half with y2 the ReLU half; kept are the raw convolution outputs, (scale, shift) tables and block outputs
+    the backward reads (encoder._ad_kept_names), all float32.  The weights carry gradients; x and kept do not."""
+    from . import encoder as E
+    return E._ad_forward(x, list(weights), tuple(strides), instance, split, eps, dtype)
+
+
+@encoder_ad.register_fake
+def _(x, weights, strides, instance, split, eps, dtype):
+    from . import encoder as E
+    return E._ad_fake(x, list(weights), tuple(strides), instance, split)
+
+
+def _encoder_ad_setup(ctx, inputs, output):
+    x, weights, strides, instance, split, eps, dtype = inputs
+    ctx.mark_non_differentiable(*output[2:])
+    ctx.save_for_backward(x, *weights, *output)
+    ctx.cfg = (len(weights), tuple(strides), bool(instance), int(split), float(eps), int(dtype))
+
+
+def _encoder_ad_backward(ctx, grads):
+    from . import encoder as E
+    nw, strides, instance, split, eps, dtype = ctx.cfg
+    x, *rest = ctx.saved_tensors
+    weights, outs = rest[:nw], rest[nw:]
+    g_y, g_y2 = grads[0], grads[1]
+    if any(g is not None and g.requires_grad for g in (g_y, g_y2)) and torch.is_grad_enabled():
+        raise NotImplementedError("dvccorr.encoder_ad has no double backward")
+    need = list(ctx.needs_input_grad[1])
+    if split < 0:
+        g_y2 = None
+        if g_y is None:
+            return None, [None] * nw, None, None, None, None, None
+        g_y = ops._f32c(g_y)
+    elif g_y is None and g_y2 is None:
+        return None, [None] * nw, None, None, None, None, None
+    return None, E._ad_backward(x, weights, strides, instance, split, eps, dtype, outs, g_y, g_y2, need), None, None, \
+        None, None, None
+
+
+torch.library.register_autograd("dvccorr::encoder_ad", _encoder_ad_backward, setup_context=_encoder_ad_setup)
+
+
+__all__ = ["encoder_ad", "enc_norm_grad", "enc_grad_add", "enc_split_grad", "enc_pack_dgrad", "enc_dgrad", "enc_wgrad", "enc_stem", "enc_conv", "enc_conv_new", "enc_stats", "enc_residual", "conv7_ad", "conv7_wgrad", "sep_gru_ad", "gru_pack_dgrad", "gru_grad_prep", "gru_dgrad", "gru_wgrad", "conv3_ad", "conv3_grad_prep", "conv3_wgrad", "conv3_pack_dgrad", "sep_gru", "conv3", "conv7_flow", "build", "lookup", "lookup_fused", "lookup_fused_proj", "corr_backward", "lookup_ad", "lookup_convc1_ad"]

@@ -971,3 +971,172 @@ def enc_residual(c3: torch.Tensor, ss3, shortcut: torch.Tensor, ss4, mode: int, 
                                  None if ss4 is None else _ptr(ss4), mode, _ptr(out), C, B, H, W, D, _stream(c3)),
           "enc_residual")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the encoders' backward (csrc/encoder_grad.hip)
+# ---------------------------------------------------------------------------------------------------------------
+def enc_grad_covers(taps: int, cin: int, cout: int) -> bool:
+    """Channel counts the backward kernels of an encoder convolution run (dvc_enc_wgrad, dvc_enc_dgrad)."""
+    return (taps in (1, 27) and cin % 8 == 0 and 8 <= cin <= _lib.ENC_MAX_COUT and 1 <= cout <= _lib.ENC_MAX_COUT
+            and cout % 8 == 0)
+
+
+def enc_wgrad_slabs(taps: int, stride: int, cin: int, cout: int, B: int, vol):
+    """(K steps, K steps per slab, slabs) of dvc_enc_wgrad's split-K (include/dvccorr.h)."""
+    ohwd = 1
+    for n in enc_out_volume(vol, stride):
+        ohwd *= n
+    nk = B * -(-ohwd // 32)
+    groups = -(-(-(-taps * cin // 16)) // (2 if taps == 1 else 7)) * -(-cout // 32)
+    want = min(-(-nk // 4), -(-_lib.ENC_WGRAD_TARGET // groups))
+    per = -(-nk // want)
+    return nk, per, -(-nk // per)
+
+
+def _enc_5d(what, *ts):
+    _need_cuda(*ts)
+    for t in ts:
+        _conv_operand(t, what)
+        if t.ndim != 5:
+            raise ValueError(f"{what} must be (B, C, H, W, D), got {tuple(t.shape)}")
+
+
+@_on_device
+def enc_norm_grad(g: torch.Tensor, x, scale_shift, mask: bool, want_gx: bool = True, want_db: bool = True):
+    """(g_x | None, db | None) of a raw convolution output x (B, C, H, W, D) from the gradient g with respect to its
+    normalised value (dvc_enc_norm_grad): gn = g [fma(x, scale, shift) > 0] under `mask`, g_x = scale (gn - mean(gn) -
+    n mean(gn n)); scale_shift None: g_x = gn with the mask [x > 0]."""
+    ts = [g] + ([x] if x is not None else [])
+    _enc_5d("enc_norm_grad: g and x", *ts)
+    if x is not None and x.shape != g.shape:
+        raise ValueError(f"enc_norm_grad: g {tuple(g.shape)} and x {tuple(x.shape)} differ")
+    if x is None and (mask or scale_shift is not None):
+        raise ValueError("enc_norm_grad: a mask or a table needs x")
+    B, C, H, W, D = g.shape
+    if scale_shift is not None:
+        _need_cuda(scale_shift)
+        _conv_operand(scale_shift, "enc_norm_grad: scale_shift")
+        if tuple(scale_shift.shape) != (B, C, 2):
+            raise ValueError(f"enc_norm_grad: scale_shift must be {(B, C, 2)}, got {tuple(scale_shift.shape)}")
+    if not (want_gx or want_db):
+        raise ValueError("enc_norm_grad: neither g_x nor db asked for")
+    nbytes = lib().dvc_enc_grad_partials_bytes(C, B, H, W, D)
+    if nbytes == 0:
+        raise ValueError(f"enc_norm_grad: bad shape {tuple(g.shape)}")
+    part = torch.empty(nbytes // 8, dtype=torch.float64, device=g.device)
+    gx = torch.empty_like(g) if want_gx else None
+    db = torch.empty(C, dtype=torch.float32, device=g.device) if want_db else None
+    check(lib().dvc_enc_norm_grad(_ptr(g), None if x is None else _ptr(x), None if scale_shift is None else
+                                  _ptr(scale_shift), 1 if mask else 0, None if gx is None else _ptr(gx),
+                                  None if db is None else _ptr(db), _ptr(part), C, B, H, W, D, _stream(g)),
+          "enc_norm_grad")
+    return gx, db
+
+
+@_on_device
+def enc_grad_add(a: torch.Tensor, b, m) -> torch.Tensor:
+    """(a + b) [m > 0], b and m optional, same shapes, contiguous float32 (dvc_enc_grad_add)."""
+    ts = [t for t in (a, b, m) if t is not None]
+    _need_cuda(*ts)
+    for t in ts:
+        _conv_operand(t, "enc_grad_add: tensors")
+        if t.shape != a.shape:
+            raise ValueError(f"enc_grad_add: shapes differ: {[tuple(v.shape) for v in ts]}")
+    dst = torch.empty_like(a)
+    check(lib().dvc_enc_grad_add(_ptr(a), None if b is None else _ptr(b), None if m is None else _ptr(m), _ptr(dst),
+                                 a.numel(), _stream(a)), "enc_grad_add")
+    return dst
+
+
+@_on_device
+def enc_split_grad(g_net, g_ctx, net: torch.Tensor, ctx: torch.Tensor) -> torch.Tensor:
+    """The gradient of the context encoder's conv2 output (B, hidden + context, ..) from the gradients of its tanh and
+    ReLU halves (either may be None: zero) and the stored halves (dvc_enc_split_grad)."""
+    ts = [t for t in (g_net, g_ctx, net, ctx) if t is not None]
+    _enc_5d("enc_split_grad: tensors", *ts)
+    if (g_net is not None and g_net.shape != net.shape) or (g_ctx is not None and g_ctx.shape != ctx.shape) or \
+            net.shape[0] != ctx.shape[0] or net.shape[2:] != ctx.shape[2:]:
+        raise ValueError(f"enc_split_grad: shapes {[tuple(v.shape) for v in ts]}")
+    B, split, H, W, D = net.shape
+    cout = split + int(ctx.shape[1])
+    g = torch.empty((B, cout, H, W, D), dtype=torch.float32, device=net.device)
+    check(lib().dvc_enc_split_grad(None if g_net is None else _ptr(g_net), None if g_ctx is None else _ptr(g_ctx),
+                                   _ptr(net), _ptr(ctx), _ptr(g), split, cout, B, H, W, D, _stream(net)),
+          "enc_split_grad")
+    return g
+
+
+def _enc_taps(weight, what):
+    if weight.ndim != 5 or tuple(weight.shape[2:]) not in ((3, 3, 3), (1, 1, 1)):
+        raise ValueError(f"{what}: weight {tuple(weight.shape)} is not a 3 x 3 x 3 or 1 x 1 x 1 convolution's")
+    return 27 if weight.shape[2] == 3 else 1
+
+
+@_on_device
+def enc_conv_pack_dgrad(weight: torch.Tensor, dtype: int) -> torch.Tensor:
+    """A (cout, cin, 3, 3, 3) or (cout, cin, 1, 1, 1) weight -> the packed operands of its input gradient
+    (dvc_enc_conv_pack_dgrad): transposed, flipped, zero biases."""
+    _need_cuda(weight)
+    taps = _enc_taps(weight, "enc_conv_pack_dgrad")
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    nbytes = lib().dvc_enc_dgrad_packed_bytes(taps, cin, cout, dtype)
+    if nbytes == 0:
+        raise NotImplementedError(f"enc_conv_pack_dgrad: cin={cin} cout={cout} taps={taps} is outside the kernel's shapes")
+    w = _f32c(weight.detach())
+    out = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
+    check(lib().dvc_enc_conv_pack_dgrad(_ptr(w), _ptr(out), taps, cin, cout, dtype, _stream(w)), "enc_conv_pack_dgrad")
+    return out
+
+
+@_on_device
+def enc_dgrad(g: torch.Tensor, packed: torch.Tensor, taps: int, stride: int, cin: int, vol, dtype: int) -> torch.Tensor:
+    """dx (B, cin) + vol of a layer with input volume `vol` from its output gradient g (B, cout, OH, OW, OD)
+    (dvc_enc_dgrad); packed from enc_conv_pack_dgrad with the same dtype."""
+    _enc_5d("enc_dgrad: g", g)
+    _need_cuda(packed)
+    vol = tuple(int(v) for v in vol)
+    if taps not in (1, 27) or stride not in (1, 2) or len(vol) != 3 or tuple(g.shape[2:]) != enc_out_volume(vol, stride):
+        raise ValueError(f"enc_dgrad: taps {taps}, stride {stride}, g {tuple(g.shape)} for an input volume {vol}")
+    B, cout = int(g.shape[0]), int(g.shape[1])
+    need = lib().dvc_enc_dgrad_packed_bytes(taps, cin, cout, dtype)
+    _check_packed("enc_dgrad", packed, need, f"taps {taps}, cin {cin}, cout {cout} and this precision take {need} "
+                  "(enc_conv_pack_dgrad with the same dtype)")
+    dx = torch.empty((B, cin) + vol, dtype=torch.float32, device=g.device)
+    check(lib().dvc_enc_dgrad(_ptr(g), _ptr(packed), _ptr(dx), taps, stride, cin, cout, B, *vol, dtype, _stream(g)),
+          "enc_dgrad")
+    return dx
+
+
+@_on_device
+def enc_wgrad(x: torch.Tensor, scale_shift, prologue: int, g: torch.Tensor, taps: int, stride: int, dtype: int) -> torch.Tensor:
+    """dW (cout, cin, k, k, k) float32 of an encoder convolution from its raw input x, the prologue the forward applied
+    to it and the output gradient g (dvc_enc_wgrad; taps 343: the stem, dvc_enc_stem_wgrad)."""
+    _enc_5d("enc_wgrad: x and g", x, g)
+    B, cin, H, W, D = x.shape
+    cout = int(g.shape[1])
+    if taps not in (1, 27, _lib.ENC_STEM_TAPS) or stride not in (1, 2) or prologue not in (0, 1, 2) or g.shape[0] != B \
+            or tuple(g.shape[2:]) != enc_out_volume((H, W, D), stride):
+        raise ValueError(f"enc_wgrad: taps {taps}, stride {stride}, prologue {prologue}, x {tuple(x.shape)}, g "
+                         f"{tuple(g.shape)}")
+    if prologue == _lib.ENC_NORM_RELU:
+        if scale_shift is None or tuple(scale_shift.shape) != (B, cin, 2):
+            raise ValueError("enc_wgrad: prologue 2 needs a (B, cin, 2) scale_shift")
+        _need_cuda(scale_shift)
+        _conv_operand(scale_shift, "enc_wgrad: scale_shift")
+    L = lib()
+    stem = taps == _lib.ENC_STEM_TAPS
+    nbytes = L.dvc_enc_stem_wgrad_workspace_bytes(stride, B, H, W, D) if stem and cin == 1 and cout == _lib.ENC_STEM_COUT \
+        else 0 if stem else L.dvc_enc_wgrad_workspace_bytes(taps, stride, cin, cout, B, H, W, D)
+    if nbytes == 0:
+        raise NotImplementedError(f"enc_wgrad: taps={taps} cin={cin} cout={cout} is outside the kernel's shapes")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    k = {1: 1, 27: 3}.get(taps, 7)
+    dw = torch.empty((cout, cin, k, k, k), dtype=torch.float32, device=x.device)
+    if stem:
+        check(L.dvc_enc_stem_wgrad(_ptr(x), _ptr(g), _ptr(dw), _ptr(ws), stride, B, H, W, D, dtype, _stream(x)),
+              "enc_stem_wgrad")
+    else:
+        check(L.dvc_enc_wgrad(_ptr(x), None if scale_shift is None else _ptr(scale_shift), prologue, _ptr(g), _ptr(dw),
+                              _ptr(ws), taps, stride, cin, cout, B, H, W, D, dtype, _stream(x)), "enc_wgrad")
+    return dw
